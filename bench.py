@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- fused megapixels/sec of the DDIF sampler on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit, higher_is_better, dtype, ms_per_step,
+the configuration).  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float32; inputs are seeded, so two
+builds can be compared output for output).  --full adds everything else the line reports: the per-class kernel timing and roofline of
+the profiled denoising steps, the bf16 drift, the strong-scaling shares, the golden parity probe, the exact-fp32 bracket and the CPU baseline.
 
 N > 1: one rank per GPU over RCCL.  Either the driver launches the ranks (`python -m torch.distributed.run ... bench.py --gpus N`:
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment) or, when WORLD_SIZE is not set, this script launches them
@@ -17,7 +22,7 @@ every rank samples its own 64 tiles, noise keyed by global tile index).
 `--config gf2_dpm50` is BASELINE.json configs[2] as stated: ONE 512x512 GF2 scene = 64 tiles split over the N ranks (STRONG
 scaling: 64 / N tiles per GPU), DPM-Solver++ 2M 50 NFE, all-gather + stitch of the scene inside the timed region.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+Prints ONE JSON line (rank 0) with the driver's contract fields plus, under --full,
   roofline     : dominant kernel class (3x3 implicit-GEMM convolutions, f16x2 split products on v_mfma_f32_32x32x16_f16) timed
                  with HIP events on the launch stream inside the timed region; `achieved` = algorithmic fp32 flops / duration,
                  `peak` = the dense 16-bit MFMA peak / the products the class issues per fp32 product (3 on the f16x2 path, 6 on
@@ -100,6 +105,9 @@ def parse_args(argv=None):
     ap.add_argument("--no-parity", action="store_true", help="skip the golden-vector parity probe of the default line (N = 1, config wv3)")
     ap.add_argument("--no-bracket", action="store_true", help="skip the exact-fp32 bracket run of the default line (a child process with DDIF_F16=0 DDIF_X3=0)")
     ap.add_argument("--no-shares", action="store_true", help="gf2_dpm50 at N = 1: skip the per-rank shares (32 / 16 / 8 tiles) behind projected_strong_scaling")
+    ap.add_argument("--full", action="store_true", help="also profile the timed steps (roofline, per-class table) and run the parity probe, the exact-fp32 "
+                                                        "bracket, the bf16 drift, the strong-scaling shares and the CPU baseline; the --no-* options above apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the arrays the last timed step returned to DIR/<name>.npy (float32, at most 64 MB)")
     return ap.parse_args(argv)
 
 
@@ -272,13 +280,15 @@ def main():
     torch.cuda.synchronize()
     if dist.is_initialized():
         dist.barrier()
-    # profiled denoising steps: about PROF_STEPS_TARGET over the whole timed region, at most one step in 10 (a profiled step is launched
-    # kernel by kernel with an event pair around each); the event buffer is sized for exactly those steps, and the library reports how
-    # many whole steps it recorded (ddif_prof_collect.steps_recorded) -- per-step figures divide by THAT
-    per_job = max(1, min(n_evals // 10 if n_evals >= 10 else 1, PROF_STEPS_TARGET // max(1, args.steps)))
-    prof_every = -(-n_evals // per_job)
-    n_prof_planned = len(range(0, n_evals, prof_every)) * args.steps
-    plan.prof_begin(prof_every, n_prof_planned * n_launch["step"])
+    prof_every, n_prof_planned = 0, 0
+    if args.full:
+        # profiled denoising steps: about PROF_STEPS_TARGET over the whole timed region, at most one step in 10 (a profiled step is launched
+        # kernel by kernel with an event pair around each); the event buffer is sized for exactly those steps, and the library reports how
+        # many whole steps it recorded (ddif_prof_collect.steps_recorded) -- per-step figures divide by THAT
+        per_job = max(1, min(n_evals // 10 if n_evals >= 10 else 1, PROF_STEPS_TARGET // max(1, args.steps)))
+        prof_every = -(-n_evals // per_job)
+        n_prof_planned = len(range(0, n_evals, prof_every)) * args.steps
+        plan.prof_begin(prof_every, n_prof_planned * n_launch["step"])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     out = None
@@ -289,6 +299,7 @@ def main():
     if dist.is_initialized():
         dist.barrier()
     dt = time.perf_counter() - t0
+    # without --full nothing was recorded: the call still names the products the plan's 3x3 convs issue (dtype below)
     prof = plan.prof_collect()
     log("timed region: %.3f s for %d step(s); %d of %d planned denoising steps profiled" % (dt, args.steps, prof["steps_recorded"], n_prof_planned))
     rccl = None
@@ -312,8 +323,10 @@ def main():
                               "note": "all_gather_into_tensor of the fused tiles (the only exchange of the path), HIP events on the launch stream, rank 0; "
                                       "bus = (N-1)/N x bytes / time (ring convention)"}}
     assert out is not None and bool(torch.isfinite(out).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sr": out})
     drift = None
-    if bf16:
+    if bf16 and args.full:
         # the same job (tiles, seed, T steps) once more on the fp32-class path: what the single bf16 product costs in the fused image
         from ddif import runtime as _rt
 
@@ -334,83 +347,54 @@ def main():
 
     mp_per_step = total * H * H / 1e6
     value = mp_per_step * args.steps / dt
-    ach_tflops = prof["total_flop"] / (prof["total_ms"] * 1e-3) / 1e12 if prof["total_ms"] > 0 else 0.0
-    step_flop_total = cost["step_flop"] * n_evals + cost["cond_flop"]
-    # the committed PMC passes are of the default (wv3, B = 64) command: other configurations report no traffic
-    traffic, traffic_info = committed_traffic() if (args.config == "wv3" and B == 64) else (None, {"traffic_from_committed_profile": False})
     x3 = "split products" in prof["kernel"] and not bf16
-    # products the dominant class issues on the matrix pipe per algorithmic fp32 product (flop-weighted over its launches: 3 = f16x2, 6 = bf16x3,
-    # 16 = exact fp32 MFMA in units of the 16-bit rate); its fp32-equivalent ceiling is the dense 16-bit MFMA peak over that
-    products = (prof["total_mfma_flop"] / prof["total_flop"]) if prof["total_flop"] > 0 else 16.0
-    peak = PEAK_BF16_MFMA_TFLOPS / products
-    ms_step = dt / args.steps * 1e3 / n_evals
-    # per-class breakdown of the profiled denoising steps (every launch of those steps sits between two HIP events)
-    n_rec = prof["steps_recorded"]
-    classes, cls_ms_total = [], 0.0
-    for c in prof["classes"]:
-        if not c["launches"] or not n_rec:
-            continue
-        ms = c["total_ms"] / n_rec
-        floor_ms = max(c["total_mfma_flop"] / (PEAK_BF16_MFMA_TFLOPS * 1e12), c["total_bytes"] / (PEAK_HBM_GBS * 1e9)) * 1e3 / n_rec
-        cls_ms_total += ms
-        classes.append({"class": c["name"], "launches_per_step": c["launches"] / n_rec, "ms_per_step": ms,
-                        "tflops": c["total_flop"] / (c["total_ms"] * 1e-3) / 1e12, "algorithmic_gbytes_per_s": c["total_bytes"] / (c["total_ms"] * 1e-3) / 1e9,
-                        "floor_ms_per_step": floor_ms, "frac_of_floor": floor_ms / ms if ms > 0 else None})
-    # the table is only printed when it adds up: sum of the classes within 15 % of the measured denoising step, no class above its floor
-    classes_ok = bool(classes) and abs(cls_ms_total - ms_step) / ms_step < 0.15 and all(c["frac_of_floor"] is None or c["frac_of_floor"] <= 1.0 for c in classes)
-    # ONE scale that does not move with the arithmetic: the step's floor = sum over the classes of max(issued 16-bit MFMA flops / dense peak,
-    # algorithmic bytes / 8 TB/s) -- a property of the launch program, not of the timing -- over the measured denoising step
-    step_floor_ms = sum(c["floor_ms_per_step"] for c in classes) if classes else None
-    step_frac = (step_floor_ms / ms_step) if step_floor_ms else None
-    if not classes_ok:
-        log("per-class table INCONSISTENT with the step (sum %.3f ms vs %.3f ms per denoising step): not reported" % (cls_ms_total, ms_step))
-    # one product per fp32 product: the dominant class's MFMA floor (flops / 2516.8 TF) drops below its HBM floor (algorithmic bytes / 8 TB/s) -- the
-    # throughput variant is priced against HBM
-    hbm_roofline = None
-    if bf16 and prof["total_ms"] > 0 and prof["total_bytes"] / (PEAK_HBM_GBS * 1e9) > prof["total_mfma_flop"] / (PEAK_BF16_MFMA_TFLOPS * 1e12):
-        ach_gbs = prof["total_bytes"] / (prof["total_ms"] * 1e-3) / 1e9
-        hbm_roofline = {
-            "bound": "hbm", "achieved": ach_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": ach_gbs / PEAK_HBM_GBS, "traffic": None,
-            "peak_note": "dominant class (3x3 convs of the 64^2 / 32^2 levels) with ONE bf16 product per fp32 product: algorithmic bytes / 8 TB/s exceeds flops / %.1f TF" % PEAK_BF16_MFMA_TFLOPS,
-            "mfma_products_per_fp32_product": products, "mfma_tflops": ach_tflops, "mfma_frac_of_dense_bf16_peak": ach_tflops * products / PEAK_BF16_MFMA_TFLOPS,
-            "algorithmic_bytes_per_launch": (prof["total_bytes"] / prof["launches"]) if prof["launches"] else None,
-            "kernel": prof["kernel"], "launches_timed": prof["launches"], "avg_launch_us": (prof["total_ms"] * 1e3 / prof["launches"]) if prof["launches"] else None,
-            "step_floor_ms": step_floor_ms, "step_frac": step_frac,
-            "whole_step": {"ms_per_denoising_step": ms_step, "tflops": step_flop_total * args.steps / dt / 1e12, "hbm_frac": (cost["step_bytes"] * n_evals + cost["cond_bytes"]) * args.steps / dt / 1e9 / PEAK_HBM_GBS,
-                           "profiled_steps": n_rec, "classes_ms_per_step_sum": cls_ms_total if classes_ok else None, "classes": classes if classes_ok else None},
-        }
-    if cf["sampler"] == "dpmpp2m":
-        metric = cf["metric"] % n_evals
-        workload = "GF2 pansharpening, one %dx%d scene = %d tiles of %dx%dx%d split over %d GPU(s) (%d per GPU), DPM-Solver++ 2M %d NFE (T=%d schedule), all-gather + stitch, fp32" % (
-            ny * H, nx * H, total, H, H, C, world, B, n_evals, T)
-    else:
-        metric = cf["metric"] % T
-        workload = "%s, batch %d of %dx%dx%d tiles per GPU, T=%d DDPM p_sample, %s" % ("WV3 pansharpening" if cf["ds"] == "wv3" else "CAVE MHIF", B, H, H, C, T,
-                                                                                        "bf16 conv operands / fp32 accumulate and tensors (throughput variant)" if bf16 else "fp32")
-    result = {
-        "metric": metric,
-        "value": value,
-        "unit": "MP/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": cf["scaling"],
-        "vs_baseline": None,
-        "dtype": "bf16" if bf16 else ("f32-class (f16x2 split)" if x3 else "f32"),
-        "data": "synthetic",
-        **({"drift": drift, "parity_configuration": False} if bf16 else {}),
-        "config": {"workload": workload, "name": args.config, "tiles_per_gpu": B, "tiles_total": total, "tile": [H, H, C], "T": T, "model_evaluations": n_evals,
-                   "sampler": cf["sampler"], "parallelism": "tile-shard x%d" % world, "launches_per_denoising_step": n_launch["step"],
-                   "plan_memory_mb": {"total": mem["total_bytes"] / 1e6, "step_activation_arena": mem["arena_bytes"] / 1e6,
-                                      "same_activations_unaliased": mem["unaliased_bytes"] / 1e6},
-                   "conv_math": ("fp32 operands pre-scaled by powers of two and split into 2 fp16 planes, 3 exact products on v_mfma_f32_32x32x16_f16, fp32 accumulate "
-                                 "(3x3 convs, low-resolution levels, q.1 of the fused attention block); 3 bf16 planes / 6 products where the operand range is open "
-                                 "(per-sample folded attention weights, wide 1x1 convs); exact fp32 MFMA elsewhere") if x3 else
-                                ("THROUGHPUT variant: conv operands rounded once to bf16, one product on v_mfma_f32_32x32x16_bf16, fp32 accumulate; tensors in HBM, GroupNorm "
-                                 "statistics, attention blocks, per-sample folded attention weights and the sampler update stay fp32 / split-product") if bf16 else "exact fp32 MFMA"},
-        "roofline": hbm_roofline if hbm_roofline else {
+    roofline = None
+    if args.full:
+        ach_tflops = prof["total_flop"] / (prof["total_ms"] * 1e-3) / 1e12 if prof["total_ms"] > 0 else 0.0
+        step_flop_total = cost["step_flop"] * n_evals + cost["cond_flop"]
+        # the committed PMC passes are of the default (wv3, B = 64) command: other configurations report no traffic
+        traffic, traffic_info = committed_traffic() if (args.config == "wv3" and B == 64) else (None, {"traffic_from_committed_profile": False})
+        # products the dominant class issues on the matrix pipe per algorithmic fp32 product (flop-weighted over its launches: 3 = f16x2, 6 = bf16x3,
+        # 16 = exact fp32 MFMA in units of the 16-bit rate); its fp32-equivalent ceiling is the dense 16-bit MFMA peak over that
+        products = (prof["total_mfma_flop"] / prof["total_flop"]) if prof["total_flop"] > 0 else 16.0
+        peak = PEAK_BF16_MFMA_TFLOPS / products
+        ms_step = dt / args.steps * 1e3 / n_evals
+        # per-class breakdown of the profiled denoising steps (every launch of those steps sits between two HIP events)
+        n_rec = prof["steps_recorded"]
+        classes, cls_ms_total = [], 0.0
+        for c in prof["classes"]:
+            if not c["launches"] or not n_rec:
+                continue
+            ms = c["total_ms"] / n_rec
+            floor_ms = max(c["total_mfma_flop"] / (PEAK_BF16_MFMA_TFLOPS * 1e12), c["total_bytes"] / (PEAK_HBM_GBS * 1e9)) * 1e3 / n_rec
+            cls_ms_total += ms
+            classes.append({"class": c["name"], "launches_per_step": c["launches"] / n_rec, "ms_per_step": ms,
+                            "tflops": c["total_flop"] / (c["total_ms"] * 1e-3) / 1e12, "algorithmic_gbytes_per_s": c["total_bytes"] / (c["total_ms"] * 1e-3) / 1e9,
+                            "floor_ms_per_step": floor_ms, "frac_of_floor": floor_ms / ms if ms > 0 else None})
+        # the table is only printed when it adds up: sum of the classes within 15 % of the measured denoising step, no class above its floor
+        classes_ok = bool(classes) and abs(cls_ms_total - ms_step) / ms_step < 0.15 and all(c["frac_of_floor"] is None or c["frac_of_floor"] <= 1.0 for c in classes)
+        # ONE scale that does not move with the arithmetic: the step's floor = sum over the classes of max(issued 16-bit MFMA flops / dense peak,
+        # algorithmic bytes / 8 TB/s) -- a property of the launch program, not of the timing -- over the measured denoising step
+        step_floor_ms = sum(c["floor_ms_per_step"] for c in classes) if classes else None
+        step_frac = (step_floor_ms / ms_step) if step_floor_ms else None
+        if not classes_ok:
+            log("per-class table INCONSISTENT with the step (sum %.3f ms vs %.3f ms per denoising step): not reported" % (cls_ms_total, ms_step))
+        # one product per fp32 product: the dominant class's MFMA floor (flops / 2516.8 TF) drops below its HBM floor (algorithmic bytes / 8 TB/s) -- the
+        # throughput variant is priced against HBM
+        hbm_roofline = None
+        if bf16 and prof["total_ms"] > 0 and prof["total_bytes"] / (PEAK_HBM_GBS * 1e9) > prof["total_mfma_flop"] / (PEAK_BF16_MFMA_TFLOPS * 1e12):
+            ach_gbs = prof["total_bytes"] / (prof["total_ms"] * 1e-3) / 1e9
+            hbm_roofline = {
+                "bound": "hbm", "achieved": ach_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": ach_gbs / PEAK_HBM_GBS, "traffic": None,
+                "peak_note": "dominant class (3x3 convs of the 64^2 / 32^2 levels) with ONE bf16 product per fp32 product: algorithmic bytes / 8 TB/s exceeds flops / %.1f TF" % PEAK_BF16_MFMA_TFLOPS,
+                "mfma_products_per_fp32_product": products, "mfma_tflops": ach_tflops, "mfma_frac_of_dense_bf16_peak": ach_tflops * products / PEAK_BF16_MFMA_TFLOPS,
+                "algorithmic_bytes_per_launch": (prof["total_bytes"] / prof["launches"]) if prof["launches"] else None,
+                "kernel": prof["kernel"], "launches_timed": prof["launches"], "avg_launch_us": (prof["total_ms"] * 1e3 / prof["launches"]) if prof["launches"] else None,
+                "step_floor_ms": step_floor_ms, "step_frac": step_frac,
+                "whole_step": {"ms_per_denoising_step": ms_step, "tflops": step_flop_total * args.steps / dt / 1e12, "hbm_frac": (cost["step_bytes"] * n_evals + cost["cond_bytes"]) * args.steps / dt / 1e9 / PEAK_HBM_GBS,
+                               "profiled_steps": n_rec, "classes_ms_per_step_sum": cls_ms_total if classes_ok else None, "classes": classes if classes_ok else None},
+            }
+        roofline = hbm_roofline if hbm_roofline else {
             "bound": "mfma",
             "achieved": ach_tflops,
             "peak": peak,
@@ -447,17 +431,50 @@ def main():
                 "classes": classes if classes_ok else None,
                 **({} if classes_ok else {"classes_error": "class sum %.3f ms vs %.3f ms per step: table withheld" % (cls_ms_total, ms_step)}),
             },
-        },
+        }
+    if cf["sampler"] == "dpmpp2m":
+        metric = cf["metric"] % n_evals
+        workload = "GF2 pansharpening, one %dx%d scene = %d tiles of %dx%dx%d split over %d GPU(s) (%d per GPU), DPM-Solver++ 2M %d NFE (T=%d schedule), all-gather + stitch, fp32" % (
+            ny * H, nx * H, total, H, H, C, world, B, n_evals, T)
+    else:
+        metric = cf["metric"] % T
+        workload = "%s, batch %d of %dx%dx%d tiles per GPU, T=%d DDPM p_sample, %s" % ("WV3 pansharpening" if cf["ds"] == "wv3" else "CAVE MHIF", B, H, H, C, T,
+                                                                                        "bf16 conv operands / fp32 accumulate and tensors (throughput variant)" if bf16 else "fp32")
+    result = {
+        "metric": metric,
+        "value": value,
+        "unit": "MP/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": cf["scaling"],
+        "vs_baseline": None,
+        "dtype": "bf16" if bf16 else ("f32-class (f16x2 split)" if x3 else "f32"),
+        "data": "synthetic",
+        **({"parity_configuration": False} if bf16 else {}),
+        **({"drift": drift} if drift else {}),
+        "config": {"workload": workload, "name": args.config, "tiles_per_gpu": B, "tiles_total": total, "tile": [H, H, C], "T": T, "model_evaluations": n_evals,
+                   "sampler": cf["sampler"], "parallelism": "tile-shard x%d" % world, "launches_per_denoising_step": n_launch["step"],
+                   "plan_memory_mb": {"total": mem["total_bytes"] / 1e6, "step_activation_arena": mem["arena_bytes"] / 1e6,
+                                      "same_activations_unaliased": mem["unaliased_bytes"] / 1e6},
+                   "conv_math": ("fp32 operands pre-scaled by powers of two and split into 2 fp16 planes, 3 exact products on v_mfma_f32_32x32x16_f16, fp32 accumulate "
+                                 "(3x3 convs, low-resolution levels, q.1 of the fused attention block); 3 bf16 planes / 6 products where the operand range is open "
+                                 "(per-sample folded attention weights, wide 1x1 convs); exact fp32 MFMA elsewhere") if x3 else
+                                ("THROUGHPUT variant: conv operands rounded once to bf16, one product on v_mfma_f32_32x32x16_bf16, fp32 accumulate; tensors in HBM, GroupNorm "
+                                 "statistics, attention blocks, per-sample folded attention weights and the sampler update stay fp32 / split-product") if bf16 else "exact fp32 MFMA"},
+        **({"roofline": roofline} if roofline else {}),
         "build_id": build_id(),
     }
     if rccl is not None:
         result["rccl"] = rccl
-    if rank == 0 and world == 1 and strong and not args.no_shares and total == 64:
+    if args.full and rank == 0 and world == 1 and strong and not args.no_shares and total == 64:
         result["projected_strong_scaling"] = strong_scaling_shares(diffusion, net, cf, C, P, H, T, n_evals, order, dev, dt / args.steps * 1e3)
     # the probe and the bracket belong to the full default line only: not to shortened profiling runs (--T), and never under a profiler -- the bracket starts a
     # child process, and a process spawned from under rocprofv3's preloaded tool is exactly the exec the GPU boxes forbid (a --pmc pass hung on it in round 6)
     profiled = any(k in os.environ for k in ("ROCPROFILER_REGISTER_LIBRARY", "ROCP_TOOL_LIBRARIES", "ROCPROF_OUTPUT_PATH")) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    full_line = rank == 0 and world == 1 and args.config == "wv3" and T == cf["T"] and not profiled
+    full_line = args.full and rank == 0 and world == 1 and args.config == "wv3" and T == cf["T"] and not profiled
     if full_line and not args.no_parity:
         result["parity"] = parity_probe(net, dev)
     if full_line and not args.no_bracket and "DDIF_X3" not in os.environ and "DDIF_F16" not in os.environ:
@@ -465,7 +482,7 @@ def main():
         if result["exact_fp32"].get("ms_per_denoising_step"):
             result["ms_per_step_exact_fp32"] = result["exact_fp32"]["ms_per_denoising_step"] * T
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("gpu result: %s" % json.dumps({k: result[k] for k in ("value", "ms_per_step")}))
         if solver is not None:  # configs[2]: the oracle's DPM-Solver++ multistep sampler on the host cores
             cb = cpu_baseline_dpmpp(sd, cfg, tiles["cond"][:8].contiguous(), diffusion.betas.cpu(), n_evals, args.cpu_seconds, args.cpu_threads)
@@ -529,7 +546,8 @@ def exact_fp32_bracket(B, H, T=100):
 
     env = dict(os.environ)
     env.update({"DDIF_F16": "0", "DDIF_X3": "0"})
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--T", str(T), "--batch", str(B), "--tile", str(H), "--no-cpu-baseline", "--no-bracket"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--T", str(T), "--batch", str(B), "--tile", str(H), "--full", "--no-cpu-baseline",
+           "--no-bracket"]
     t0 = time.perf_counter()
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -665,31 +683,36 @@ def bench_training(args, cf, rank, world, dev):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert bool(torch.isfinite(loss.detach()).all())
-    # algorithmic flops of one iteration: forward + backward = 3 x the un-hoisted forward (dgrad + wgrad = 2 x forward), plus one
-    # forward per self-conditioning pass actually run
-    cost = d._plan(cond, train=True).cost()
-    fwd_flop = cost["step_flop"] + cost["cond_flop"]
-    step_flop = fwd_flop * (3.0 + sc_passes[0] / max(1, args.steps))
-    tf = step_flop * args.steps / dt / 1e12
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().reshape(1), "params": torch.cat([p.detach().reshape(-1) for p in params])})
+    roofline = None
+    if args.full:
+        # algorithmic flops of one iteration: forward + backward = 3 x the un-hoisted forward (dgrad + wgrad = 2 x forward), plus one
+        # forward per self-conditioning pass actually run
+        cost = d._plan(cond, train=True).cost()
+        fwd_flop = cost["step_flop"] + cost["cond_flop"]
+        step_flop = fwd_flop * (3.0 + sc_passes[0] / max(1, args.steps))
+        tf = step_flop * args.steps / dt / 1e12
+        roofline = {"bound": "mfma", "achieved": tf, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": tf / PEAK_F32_MFMA_TFLOPS, "traffic": None,
+                    "algorithmic_gflop_per_iteration": step_flop / 1e9,
+                    "peak_note": "whole training iteration: algorithmic flops (3 x un-hoisted forward + self-conditioning forwards) / wall time vs the dense fp32 "
+                                 "matrix peak; forward / dgrad convs and the 3x3 weight gradients (conv3x3_wgrad_x3_kernel, DDIF_WGRAD_X3=1) run bf16x3 split products, "
+                                 "the exact fp32 MFMA weight-gradient kernel remains the fallback for widths that are not a multiple of 8 or exceed 128",
+                    "path": "native reverse launch program (csrc/ddif_train.cpp, ddif_plan_train_step): NHWC end to end, device-side weight refresh"}
     if rank == 0:
         line = {"metric": cf["metric"] % T, "value": world * B * args.steps / dt, "unit": "tiles/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                 "config": {"workload": "sr3_dwt training iteration (q_sample, 50 %% self-conditioning pass, forward, backward, DDP all-reduce, clip + AdamW + EMA), "
                                        "WV3 %dx%dx%d tiles, batch %d per GPU, fp32" % (H, H, C, B), "name": args.config, "tiles_per_gpu": B, "tile": [H, H, C],
                            "T": T, "parallelism": "ddp x%d" % world, "self_conditioning_passes_in_timed_region": sc_passes[0]},
-                "roofline": {"bound": "mfma", "achieved": tf, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": tf / PEAK_F32_MFMA_TFLOPS, "traffic": None,
-                             "algorithmic_gflop_per_iteration": step_flop / 1e9,
-                             "peak_note": "whole training iteration: algorithmic flops (3 x un-hoisted forward + self-conditioning forwards) / wall time vs the dense fp32 "
-                                          "matrix peak; forward / dgrad convs and the 3x3 weight gradients (conv3x3_wgrad_x3_kernel, DDIF_WGRAD_X3=1) run bf16x3 split products, "
-                                          "the exact fp32 MFMA weight-gradient kernel remains the fallback for widths that are not a multiple of 8 or exceed 128",
-                             "path": "native reverse launch program (csrc/ddif_train.cpp, ddif_plan_train_step): NHWC end to end, device-side weight refresh"},
+                **({"roofline": roofline} if roofline else {}),
                 "build_id": build_id()}
         if dist.is_initialized():
             line["allreduce"] = {"bytes": 4 * n_param, "ms_per_iteration": comm_ms[0] / args.steps,
                                  "algorithmic_gbytes_per_s": 4 * n_param / (comm_ms[0] / args.steps * 1e-3) / 1e9 if comm_ms[0] > 0 else None,
                                  "bus_gbytes_per_s": 2.0 * (world - 1) / world * 4 * n_param / (comm_ms[0] / args.steps * 1e-3) / 1e9 if comm_ms[0] > 0 else None,
                                  "note": "one flat fp32 bucket, RCCL ring all-reduce (AVG); timed with HIP events around the collective, rank 0"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_training(sd, cfg, tiles, T, args.cpu_seconds, args.cpu_threads)
             line["vs_cpu_baseline"] = line["value"] / line["cpu_baseline"]["value"]
         print(json.dumps(line), flush=True)
@@ -739,6 +762,28 @@ def cpu_baseline_training(sd, cfg, tiles, T, budget_s, threads=0):
             "sample": "%d training iterations (q_sample, oracle forward, L1, autograd backward, clip 0.003, AdamW) on a batch of %d WV3 64x64 tiles, %.1f s; no "
                       "self-conditioning pass, Dropout / DropPath off (both add work on the reference's side)" % (n, bsz, dt),
             "host_cpus": os.cpu_count()}
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000 - 4096  # --dump-outputs: 64 MB in all, .npy headers included
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float32.  Smallest first, an array gets at most an equal share of what the limit has left
+    (DUMP_LIMIT_BYTES in all); one that does not fit is cut to a fixed sample of its elements (seed 0, sorted flat indices), the same for every run
+    with the same arguments."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_LIMIT_BYTES // 4
+    names = sorted(arrays, key=lambda k: arrays[k].numel())
+    for i, name in enumerate(names):
+        a = arrays[name].detach().float().cpu().numpy()
+        keep = min(a.size, left // (len(names) - i))
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        left -= keep
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log("outputs of the last timed step written to %s: %s" % (dirname, ", ".join("%s %s" % (k, tuple(v.shape)) for k, v in arrays.items())))
 
 
 def committed_traffic():
