@@ -265,7 +265,7 @@ int ddif_plan_sample_ddpm(ddif_plan_t plan, const ddif_ddpm_tables* tabs, const 
                           uint64_t tile0, float clamp_lo, float clamp_hi, int do_clamp, float* out, void* stream) {
     DDIF_GUARD_BEGIN
     DDIF_PLAN_ENTER(plan, "ddif_plan call");
-    return plan->p.sample_ddpm(tabs, x_T, noise, seed, tile0, clamp_lo, clamp_hi, do_clamp, out, (hipStream_t)stream);
+    return plan->p.sample_ddpm(tabs, nullptr, x_T, noise, seed, tile0, clamp_lo, clamp_hi, do_clamp, out, (hipStream_t)stream);
     DDIF_GUARD_END
 }
 
@@ -273,7 +273,7 @@ int ddif_plan_sample_ddim(ddif_plan_t plan, const ddif_ddim_tables* tabs, const 
                           uint64_t tile0, float clamp_lo, float clamp_hi, int do_clamp, float* out, void* stream) {
     DDIF_GUARD_BEGIN
     DDIF_PLAN_ENTER(plan, "ddif_plan call");
-    return plan->p.sample_ddim(tabs, x_T, noise, seed, tile0, clamp_lo, clamp_hi, do_clamp, out, (hipStream_t)stream);
+    return plan->p.sample_ddim(tabs, nullptr, x_T, noise, seed, tile0, clamp_lo, clamp_hi, do_clamp, out, (hipStream_t)stream);
     DDIF_GUARD_END
 }
 
@@ -291,6 +291,53 @@ int ddif_plan_q_sample_forward(ddif_plan_t plan, const float* x0, const float* n
     DDIF_GUARD_BEGIN
     DDIF_PLAN_ENTER(plan, "ddif_plan call");
     return plan->p.q_sample_forward(x0, noise, sqrt_ac_host, sqrt_1mac_host, time_host, self_cond, pred, (hipStream_t)stream);
+    DDIF_GUARD_END
+}
+
+int ddif_plan_set_objective(ddif_plan_t plan, int pred_mode, int loss_type) {
+    DDIF_GUARD_BEGIN
+    DDIF_PLAN_ENTER(plan, "ddif_plan_set_objective");
+    return plan->p.set_objective(pred_mode, loss_type);
+    DDIF_GUARD_END
+}
+
+int ddif_plan_get_objective(ddif_plan_t plan, int* pred_mode, int* loss_type) {
+    if (!plan) return ddif::fail(DDIF_ERR_INVALID, "ddif_plan_get_objective: NULL plan");
+    if (pred_mode) *pred_mode = plan->p.pred_mode;
+    if (loss_type) *loss_type = plan->p.loss_type;
+    return DDIF_OK;
+}
+
+int ddif_plan_sample_ddpm_ex(ddif_plan_t plan, const ddif_ddpm_tables* tabs, const ddif_pred_tables* pred, const float* x_T, const float* noise, uint64_t seed,
+                             uint64_t tile0, float clamp_lo, float clamp_hi, int do_clamp, float* out, void* stream) {
+    DDIF_GUARD_BEGIN
+    DDIF_PLAN_ENTER(plan, "ddif_plan_sample_ddpm_ex");
+    return plan->p.sample_ddpm(tabs, pred, x_T, noise, seed, tile0, clamp_lo, clamp_hi, do_clamp, out, (hipStream_t)stream);
+    DDIF_GUARD_END
+}
+
+int ddif_plan_sample_ddim_ex(ddif_plan_t plan, const ddif_ddim_tables* tabs, const ddif_pred_tables* pred, const float* x_T, const float* noise, uint64_t seed,
+                             uint64_t tile0, float clamp_lo, float clamp_hi, int do_clamp, float* out, void* stream) {
+    DDIF_GUARD_BEGIN
+    DDIF_PLAN_ENTER(plan, "ddif_plan_sample_ddim_ex");
+    return plan->p.sample_ddim(tabs, pred, x_T, noise, seed, tile0, clamp_lo, clamp_hi, do_clamp, out, (hipStream_t)stream);
+    DDIF_GUARD_END
+}
+
+int ddif_plan_q_sample_forward_ex(ddif_plan_t plan, const float* x0, const float* noise, const float* sqrt_ac_host, const float* sqrt_1mac_host,
+                                  const float* time_host, const float* self_cond, const ddif_objective_rows* rows, float* pred, float* recon, void* stream) {
+    DDIF_GUARD_BEGIN
+    DDIF_PLAN_ENTER(plan, "ddif_plan_q_sample_forward_ex");
+    return plan->p.q_sample_forward(x0, noise, sqrt_ac_host, sqrt_1mac_host, time_host, self_cond, pred, (hipStream_t)stream, rows, recon);
+    DDIF_GUARD_END
+}
+
+int ddif_plan_train_step_ex(ddif_plan_t plan, const float* x0, const float* noise, const float* sqrt_ac_host, const float* sqrt_1mac_host, const float* time_host,
+                            const float* self_cond, const ddif_objective_rows* rows, float* loss_dev, float* pred, float* recon, void* stream) {
+    DDIF_GUARD_BEGIN
+    DDIF_PLAN_ENTER(plan, "ddif_plan_train_step_ex");
+    if (!plan->p.net->dgrad_filled) return ddif::fail(DDIF_ERR_STATE, "ddif_plan_train_step_ex: the gradient-conv weight packs are still empty -- call ddif_net_refresh after creating the train-mode plan (and after every re-commit)");
+    return plan->p.train_step(x0, noise, sqrt_ac_host, sqrt_1mac_host, time_host, self_cond, loss_dev, pred, (hipStream_t)stream, rows, recon);
     DDIF_GUARD_END
 }
 

@@ -17,6 +17,8 @@ ConvVariant get_conv_variant_k3e(int stride, int ups, int ck, int pro, int cfg, 
         if (pro == PRO_GN_SILU) { v = variant_for_cfg<3, 1, 0, 16, PRO_GN_SILU, 1, EPI_TBS>(cfg); v.name = "conv3x3_gn_silu_tbs"; }
     } else if (epi == EPI_SAMP) {
         if (pro == PRO_GN_SILU && cfg >= 7 && cfg != 20 && cfg != 21) { v = variant_for_cfg<3, 1, 0, 16, PRO_GN_SILU, 1, EPI_SAMP>(cfg); v.name = "conv3x3_gn_silu_sampler"; }
+    } else if (epi == (EPI_SAMP | EPI_PRED)) {  // noise / v prediction: the same tilings with the conversion to x0 in front of the update
+        if (pro == PRO_GN_SILU && cfg >= 7 && cfg != 20 && cfg != 21) { v = variant_for_cfg<3, 1, 0, 16, PRO_GN_SILU, 1, EPI_SAMP | EPI_PRED>(cfg); v.name = "conv3x3_gn_silu_sampler_pred"; }
     } else if (epi == EPI_SILU) {
         if (pro == PRO_NONE) { v = variant_for_cfg<3, 1, 0, 16, PRO_NONE, 1, EPI_SILU>(cfg); v.name = "conv3x3_silu"; }
     }

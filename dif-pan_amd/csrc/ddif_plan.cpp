@@ -497,6 +497,17 @@ int Plan::add_conv(std::vector<Op>& prog, const ConvSpec& s, Tensor* out) {
             final_fused = true;
         }
     }
+    // ... and with the noise / v prediction turned into x0 in front of the update (EPI_PRED: its own instantiation, ddif_plan_set_objective)
+    ConvKernelFn fn_samp_pred = nullptr;
+    if (fn_samp) {
+        const ConvVariant vp = get_conv_variant(pc.ks, s.stride, s.ups, pc.ck, s.pro, cfg, vec, EPI_SAMP | EPI_PRED, math);
+        if (vp.fn && vp.smem == var.smem) {
+            fn_samp_pred = vp.fn;
+            if (var.smem + 8192 > 64 * 1024)
+                DDIF_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn_samp_pred), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(var.smem + 8192)));
+            final_fused_pred = true;
+        }
+    }
     const float* lms_p = lms.p;
     const bool dyn = s.dyn_input;
     const bool self_c = net->cfg.self_condition != 0;
@@ -528,7 +539,7 @@ int Plan::add_conv(std::vector<Op>& prog, const ConvSpec& s, Tensor* out) {
         if (var.f16) ++n_conv3_f16;
         if (var.b1) ++n_conv3_b1;
     }
-    op.run = [a, var, fn_tbs, fn_samp, lms_p, grid, block, smem, dyn, self_c, tb_off](hipStream_t st, const StepCtx& ctx) {
+    op.run = [a, var, fn_tbs, fn_samp, fn_samp_pred, lms_p, grid, block, smem, dyn, self_c, tb_off](hipStream_t st, const StepCtx& ctx) {
         ConvArgs aa = a;
         const dim3 g = grid;
         if (dyn) {
@@ -553,7 +564,7 @@ int Plan::add_conv(std::vector<Op>& prog, const ConvSpec& s, Tensor* out) {
             aa.s_step_next = ctx.step_next;
             aa.s_kind = ctx.samp_kind;
             aa.step_ptr = ctx.step_ptr;
-            hipLaunchKernelGGL(fn_samp, g, block, smem, st, aa);
+            hipLaunchKernelGGL(ctx.samp_pred ? fn_samp_pred : fn_samp, g, block, smem, st, aa);
             return;
         }
         hipLaunchKernelGGL((tb_off >= 0 && ctx.tb_stride != 0) ? fn_tbs : var.fn, g, block, smem, st, aa);
@@ -1669,7 +1680,7 @@ void dw3x3_plain(hipStream_t s, const float* in, int C, int B, int H, int W, con
 // One training iteration's device work (reference diffusion_ddpm_pan.py:692-766 main pass + diffusion_engine.py:233 loss.backward()):
 // x_t = a x0 + s noise, train-mode forward (masks as set), L1 loss against x0, reverse program -> gradients in the bound tensors.
 int Plan::train_step(const float* x0, const float* noise, const float* a_h, const float* s_h, const float* t_h, const float* sc, float* loss_dev, float* pred,
-                     hipStream_t s) {
+                     hipStream_t s, const ddif_objective_rows* rows, float* recon_out) {
     if (!train_mode || bwd.empty()) return fail(DDIF_ERR_STATE, "ddif_plan_train_step: not a train-mode plan");
     if (!cond_set) return fail(DDIF_ERR_STATE, "ddif_plan_train_step before ddif_plan_set_cond");
     if (!x0 || !noise || !a_h || !s_h || !t_h) return fail(DDIF_ERR_INVALID, "ddif_plan_train_step: NULL argument");
@@ -1682,9 +1693,59 @@ int Plan::train_step(const float* x0, const float* noise, const float* a_h, cons
     DDIF_HIPCHK(hipMemcpyAsync(small + B, s_h, (size_t)B * sizeof(float), hipMemcpyDefault, s));
     hipLaunchKernelGGL(nchw_to_nhwc_kernel, ew_grid(n), dim3(256), 0, s, x0, B, C, HW, 0, C, img[0]);
     hipLaunchKernelGGL(nchw_to_nhwc_kernel, ew_grid(n), dim3(256), 0, s, noise, B, C, HW, 0, C, img[1]);
-    hipLaunchKernelGGL(q_sample_kernel, ew_grid(n), dim3(256), 0, s, (const float*)img[0], (const float*)img[1], (const float*)small, (const float*)(small + B), B, (size_t)HW * C, x_in.p);
+    const bool p2 = rows && rows->p2_weight;
+    if (pred_mode != DDIF_PRED_X_START || p2 || recon_out)
+        if (int e = objective_rows(rows, p2, s)) return e;
+    const float* target = img[0];  // x_start (:729-732)
+    if (pred_mode == DDIF_PRED_V) {  // v = a noise - s x0 (:734), written by the pass that writes x_t
+        if (!vtarget)
+            if (int e = dalloc(&vtarget, n)) return e;
+        hipLaunchKernelGGL(q_sample_v_kernel, ew_grid(n), dim3(256), 0, s, (const float*)img[0], (const float*)img[1], (const float*)small, (const float*)(small + B), B, (size_t)HW * C, x_in.p, vtarget);
+        target = vtarget;
+    } else {
+        hipLaunchKernelGGL(q_sample_kernel, ew_grid(n), dim3(256), 0, s, (const float*)img[0], (const float*)img[1], (const float*)small, (const float*)(small + B), B, (size_t)HW * C, x_in.p);
+        if (pred_mode == DDIF_PRED_NOISE) target = img[1];  // the noise itself (:726-728)
+    }
     if (sc) hipLaunchKernelGGL(nchw_to_nhwc_kernel, ew_grid(n), dim3(256), 0, s, sc, B, C, HW, 0, C, sc_in.p);
-    return train_core(t_h, sc != nullptr, img[0], loss_dev, pred, s);
+    if (int e = train_core(t_h, sc != nullptr, target, loss_dev, pred, s, p2 ? obj_rows + 2 * (size_t)B : nullptr)) return e;
+    if (recon_out) {
+        // recon_x0 (:724, :730, :735): the reference rebuilds it from the prediction for noise and from the TRUE v for pred_v
+        if (pred_mode == DDIF_PRED_X_START) hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid(n), dim3(256), 0, s, (const float*)net_out.p, B, C, HW, recon_out);
+        else if (int e = recon(pred_mode == DDIF_PRED_V ? vtarget : net_out.p, recon_out, true, s)) return e;
+        DDIF_HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+// ---- objective (include/ddif.h ddif_plan_set_objective)
+int Plan::set_objective(int pred, int loss) {
+    if (pred != DDIF_PRED_X_START && pred != DDIF_PRED_NOISE && pred != DDIF_PRED_V) return fail(DDIF_ERR_INVALID, "ddif_plan_set_objective: pred_mode %d (0 x_start, 1 noise, 2 pred_v)", pred);
+    if (loss != DDIF_LOSS_L1 && loss != DDIF_LOSS_L2) return fail(DDIF_ERR_INVALID, "ddif_plan_set_objective: loss_type %d (0 l1, 1 l2)", loss);
+    if ((pred != DDIF_PRED_X_START) != (pred_mode != DDIF_PRED_X_START)) drop_graphs();  // the captured step holds the other final-conv instantiation
+    pred_mode = pred;
+    loss_type = loss;
+    return 0;
+}
+// device copies of the caller's per-sample rows (host or device source, like sqrt_ac / sqrt_1mac)
+int Plan::objective_rows(const ddif_objective_rows* rows, bool need_p2, hipStream_t s) {
+    const bool need_rec = pred_mode != DDIF_PRED_X_START;
+    if ((need_rec || need_p2) && !rows) return fail(DDIF_ERR_INVALID, "the plan's objective needs ddif_objective_rows");
+    if (need_rec && (!rows->recon_xt || !rows->recon_out)) return fail(DDIF_ERR_INVALID, "ddif_objective_rows: recon_xt / recon_out are required for a noise / v prediction");
+    if (!obj_rows)
+        if (int e = dalloc(&obj_rows, (size_t)3 * B)) return e;
+    if (need_rec) {
+        DDIF_HIPCHK(hipMemcpyAsync(obj_rows, rows->recon_xt, (size_t)B * sizeof(float), hipMemcpyDefault, s));
+        DDIF_HIPCHK(hipMemcpyAsync(obj_rows + B, rows->recon_out, (size_t)B * sizeof(float), hipMemcpyDefault, s));
+    }
+    if (need_p2) DDIF_HIPCHK(hipMemcpyAsync(obj_rows + 2 * (size_t)B, rows->p2_weight, (size_t)B * sizeof(float), hipMemcpyDefault, s));
+    return 0;
+}
+int Plan::recon(const float* src_nhwc, float* out, bool nchw, hipStream_t s) {
+    const int HW = H * W;
+    hipLaunchKernelGGL(recon_x0_kernel, ew_grid((size_t)B * HW * C), dim3(256), 0, s, (const float*)x_in.p, src_nhwc, (const float*)obj_rows, (const float*)(obj_rows + B), B, C, HW,
+                       nchw ? 1 : 0, out);
+    DDIF_HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // forward + loss + reverse pass on a GIVEN network input (parity tests feed the reference's own x / target): x, target (B,C,H,W)
@@ -1703,7 +1764,7 @@ int Plan::train_forward_backward(const float* x, const float* t_h, const float* 
     return train_core(t_h, sc != nullptr, img[0], loss_dev, pred, s);
 }
 
-int Plan::train_core(const float* t_h, bool has_sc, const float* target_nhwc, float* loss_dev, float* pred, hipStream_t s) {
+int Plan::train_core(const float* t_h, bool has_sc, const float* target_nhwc, float* loss_dev, float* pred, hipStream_t s, const float* p2w) {
     const int HW = H * W;
     const size_t n = (size_t)B * HW * C;
     if (int e = time_rows_aux(t_h, B, taux, s)) return e;
@@ -1714,7 +1775,7 @@ int Plan::train_core(const float* t_h, bool has_sc, const float* target_nhwc, fl
     ctx.tb_stride = net->nslots;
     train_set_stem_source(ctx.sc);
     run_prog(step, s, ctx, false);
-    if (int e = train_backward(target_nhwc, 1.0f, loss_dev, s)) return e;
+    if (int e = train_backward(target_nhwc, 1.0f, loss_dev, s, p2w)) return e;
     if (pred) hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid(n), dim3(256), 0, s, (const float*)net_out.p, B, C, HW, pred);
     DDIF_HIPCHK(hipGetLastError());
     return 0;
@@ -1826,7 +1887,7 @@ static int check_sampler_net(const Net* n) {
 // Shared loop of the DDPM (kind 0) and DDIM (kind 1) samplers.  Everything that changes from step to step is read
 // from device memory (step counter, coefficient tables, SamplerRun), so two consecutive steps (img0 -> img1 -> img0)
 // are captured ONCE into a hipGraph and replayed: ~270 launches per replay instead of per-kernel host launches.
-int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int n_tabs, const float* t_model, const float* xT,
+int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int n_tabs, const ddif_pred_tables* pred_tabs, const float* t_model, const float* xT,
                       const float* noise, uint64_t seed, uint64_t tile0, float lo, float hi, int do_clamp, float* out, hipStream_t s) {
     if (int e = check_sampler_net(net)) return e;
     if (side_pending) {  // a train-mode plan: the cond-only side work must not be waited for inside a captured step
@@ -1846,7 +1907,7 @@ int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int 
     }
     if (tabs_cap < n_steps) {
         drop_graphs();
-        if (int e = dalloc(&d_tabs, (size_t)6 * n_steps)) return e;
+        if (int e = dalloc(&d_tabs, (size_t)8 * n_steps)) return e;
         tabs_cap = n_steps;
     }
     SamplerRun run{};
@@ -1861,6 +1922,17 @@ int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int 
         run.tab[i] = d_tabs + (size_t)i * tabs_cap;
         DDIF_HIPCHK(hipMemcpyAsync(d_tabs + (size_t)i * tabs_cap, tabs_host[i], (size_t)n_steps * sizeof(float), hipMemcpyHostToDevice, s));
     }
+    const bool pred = pred_mode != DDIF_PRED_X_START;
+    if (pred) {  // the two coefficients of the prediction -> x0 conversion (sampler_dev.h pred_x0)
+        if (!pred_tabs || pred_tabs->n_steps != n_steps || !pred_tabs->coef_xt || !pred_tabs->coef_out)
+            return fail(DDIF_ERR_INVALID, "sampler: the plan's objective is a noise / v prediction (ddif_plan_set_objective) -- the _ex entry point with ddif_pred_tables of %d steps is needed", n_steps);
+        const float* pt[2] = {pred_tabs->coef_xt, pred_tabs->coef_out};
+        for (int i = 0; i < 2; ++i) {
+            run.tab[6 + i] = d_tabs + (size_t)(6 + i) * tabs_cap;
+            DDIF_HIPCHK(hipMemcpyAsync(d_tabs + (size_t)(6 + i) * tabs_cap, pt[i], (size_t)n_steps * sizeof(float), hipMemcpyHostToDevice, s));
+        }
+    }
+    const bool fused = pred ? final_fused_pred : final_fused;
     DDIF_HIPCHK(hipMemcpyAsync(d_run, &run, sizeof(run), hipMemcpyHostToDevice, s));
     DDIF_HIPCHK(hipMemsetAsync(d_step, 0, 2 * sizeof(int), s));
     // the host copies above must have been consumed before `run` (stack) goes away: pageable H2D copies are staged
@@ -1875,7 +1947,8 @@ int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int 
         ctx.step_next = d_step + (parity ^ 1);
         ctx.samp_run = d_run;
         ctx.samp_kind = kind;
-        ctx.samp_out = final_fused ? img[parity ^ 1] : nullptr;
+        ctx.samp_out = fused ? img[parity ^ 1] : nullptr;
+        ctx.samp_pred = pred;
         ctx.tb_rowstride = net->nslots;
         run_prog(step, st, ctx, prof);
         StepArgs a{};
@@ -1887,7 +1960,8 @@ int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int 
         a.C = C;
         a.HW = HW;
         a.run = reinterpret_cast<const SamplerRun*>(d_run);
-        if (final_fused) return;  // the update ran in the final conv's epilogue, which also wrote the next step's counter
+        a.pred = pred ? 1 : 0;
+        if (fused) return;  // the update ran in the final conv's epilogue, which also wrote the next step's counter
         a.step = d_step + parity;
         if (kind == 0) hipLaunchKernelGGL(ddpm_step_kernel, ew_grid(n), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(ddim_step_kernel, ew_grid(n), dim3(256), 0, st, a);
@@ -2009,22 +2083,22 @@ int Plan::train_random_masks(uint64_t seed, uint64_t tile0, float p_drop, float 
     return 0;
 }
 
-int Plan::sample_ddpm(const ddif_ddpm_tables* t, const float* xT, const float* noise, uint64_t seed, uint64_t tile0,
+int Plan::sample_ddpm(const ddif_ddpm_tables* t, const ddif_pred_tables* pt, const float* xT, const float* noise, uint64_t seed, uint64_t tile0,
                       float lo, float hi, int do_clamp, float* out, hipStream_t s) {
     if (!cond_set) return fail(DDIF_ERR_STATE, "ddif_plan_sample_ddpm before ddif_plan_set_cond");
     if (!t || t->n_steps < 1 || !t->t_model || !t->coef_x0 || !t->coef_xt || !t->coef_z || !out)
         return fail(DDIF_ERR_INVALID, "ddif_plan_sample_ddpm: bad tables");
     const float* tabs[3] = {t->coef_x0, t->coef_xt, t->coef_z};
-    return run_sampler(0, t->n_steps, tabs, 3, t->t_model, xT, noise, seed, tile0, lo, hi, do_clamp, out, s);
+    return run_sampler(0, t->n_steps, tabs, 3, pt, t->t_model, xT, noise, seed, tile0, lo, hi, do_clamp, out, s);
 }
 
-int Plan::sample_ddim(const ddif_ddim_tables* t, const float* xT, const float* noise, uint64_t seed, uint64_t tile0,
+int Plan::sample_ddim(const ddif_ddim_tables* t, const ddif_pred_tables* pt, const float* xT, const float* noise, uint64_t seed, uint64_t tile0,
                       float lo, float hi, int do_clamp, float* out, hipStream_t s) {
     if (!cond_set) return fail(DDIF_ERR_STATE, "ddif_plan_sample_ddim before ddif_plan_set_cond");
     if (!t || t->n_steps < 1 || !t->t_model || !t->sqrt_recip || !t->sqrt_recipm1 || !t->sqrt_ap || !t->dir_coef || !t->sigma || !out)
         return fail(DDIF_ERR_INVALID, "ddif_plan_sample_ddim: bad tables");
     const float* tabs[5] = {t->sqrt_recip, t->sqrt_recipm1, t->sqrt_ap, t->dir_coef, t->sigma};
-    return run_sampler(1, t->n_steps, tabs, 5, t->t_model, xT, noise, seed, tile0, lo, hi, do_clamp, out, s);
+    return run_sampler(1, t->n_steps, tabs, 5, pt, t->t_model, xT, noise, seed, tile0, lo, hi, do_clamp, out, s);
 }
 
 int Plan::sample_dpmpp(const ddif_dpm_tables* t, const float* xT, float lo, float hi, int do_clamp, float* out, hipStream_t s) {
@@ -2052,7 +2126,7 @@ int Plan::sample_dpmpp(const ddif_dpm_tables* t, const float* xT, float lo, floa
         float* mnew = mbuf[slot];
         slot = (slot + 1) % 3;
         hipLaunchKernelGGL(dpm_x0_kernel, ew_grid(n), dim3(256), 0, s, (const float*)net_out.p, (const float*)img[cur], (const float*)lms.p,
-                           t->alpha[k], t->sigma[k], lo, hi, do_clamp, n, mnew);
+                           t->alpha[k], t->sigma[k], lo, hi, do_clamp, pred_mode, n, mnew);
         hist[2] = hist[1];
         hist[1] = hist[0];
         hist[0] = mnew;
@@ -2084,10 +2158,12 @@ int Plan::sample_dpmpp(const ddif_dpm_tables* t, const float* xT, float lo, floa
 }
 
 int Plan::q_sample_forward(const float* x0, const float* noise, const float* a_h, const float* s_h, const float* t_h,
-                           const float* sc, float* pred, hipStream_t s) {
+                           const float* sc, float* pred, hipStream_t s, const ddif_objective_rows* rows, float* recon_out) {
     if (!cond_set) return fail(DDIF_ERR_STATE, "ddif_plan_q_sample_forward before ddif_plan_set_cond");
-    if (!x0 || !noise || !a_h || !s_h || !t_h || !pred) return fail(DDIF_ERR_INVALID, "ddif_plan_q_sample_forward: NULL argument");
+    if (!x0 || !noise || !a_h || !s_h || !t_h || (!pred && !recon_out)) return fail(DDIF_ERR_INVALID, "ddif_plan_q_sample_forward: NULL argument");
     if (int e = check_sampler_net(net)) return e;
+    if (recon_out && pred_mode != DDIF_PRED_X_START)
+        if (int e = objective_rows(rows, false, s)) return e;
     const int HW = H * W;
     const size_t n = (size_t)B * HW * C;
     DDIF_HIPCHK(hipMemcpyAsync(small, a_h, (size_t)B * sizeof(float), hipMemcpyDefault, s));  // host or device source
@@ -2103,7 +2179,11 @@ int Plan::q_sample_forward(const float* x0, const float* noise, const float* a_h
     ctx.tb = tb;
     ctx.tb_stride = net->nslots;
     run_prog(step, s, ctx, false);
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid(n), dim3(256), 0, s, (const float*)net_out.p, B, C, HW, pred);
+    if (pred) hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid(n), dim3(256), 0, s, (const float*)net_out.p, B, C, HW, pred);
+    if (recon_out) {  // the x0 the self-conditioning pass feeds back (:708-713)
+        if (pred_mode == DDIF_PRED_X_START) hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid(n), dim3(256), 0, s, (const float*)net_out.p, B, C, HW, recon_out);
+        else if (int e = recon(net_out.p, recon_out, true, s)) return e;
+    }
     DDIF_HIPCHK(hipGetLastError());
     return 0;
 }

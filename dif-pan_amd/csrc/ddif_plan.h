@@ -27,6 +27,7 @@ struct StepCtx {
     const void* samp_run = nullptr; // device SamplerRun
     int* step_next = nullptr;       // the counter the NEXT step reads
     int samp_kind = 0;
+    bool samp_pred = false;         // the conv output is a noise / v prediction: the EPI_PRED instantiation converts it to x0 first
 };
 
 struct Op {
@@ -185,6 +186,10 @@ struct Plan {
     float* small = nullptr;           // device scratch for per-sample coefficient arrays (2*B floats)
     // sampler run state (device) + hipGraph replay of a pair of denoising steps
     int* d_step = nullptr;              // two counters: a step's kernels read d_step[parity], the sampler update writes d_step[parity ^ 1]
+    bool final_fused_pred = false;      // ... and its EPI_PRED twin exists too (noise / v prediction)
+    // objective (ddif_plan_set_objective; sticky): what the network output means and which loss the training step takes.  Defaults = the engine's.
+    int pred_mode = DDIF_PRED_X_START, loss_type = DDIF_LOSS_L1;
+    int set_objective(int pred, int loss);
     bool final_fused = false;           // the final conv carries the sampler epilogue: no separate update / counter launches in the DDPM / DDIM loops
     int math_mode = 0;                  // g_math_mode / g_f16_raw at creation: one plan is built under ONE arithmetic even when the process-wide switches change while it builds
     int f16_raw = 1;
@@ -273,11 +278,15 @@ struct Plan {
     float* d_net_out = nullptr;       // d(loss)/d(net_out), NHWC
     int build_backward();
     int train_step(const float* x0, const float* noise, const float* a_h, const float* s_h, const float* t_h, const float* sc, float* loss_dev, float* pred,
-                   hipStream_t s);
+                   hipStream_t s, const ddif_objective_rows* rows = nullptr, float* recon = nullptr);
     int train_bind(int n, const char* const* keys, float* const* grads);
     int train_forward_backward(const float* x, const float* t_h, const float* sc, const float* target, float* loss_dev, float* pred, hipStream_t s);
-    int train_core(const float* t_h, bool has_sc, const float* target_nhwc, float* loss_dev, float* pred, hipStream_t s);
-    int train_backward(const float* target_nhwc, float upstream, float* loss_dev, hipStream_t s);
+    int train_core(const float* t_h, bool has_sc, const float* target_nhwc, float* loss_dev, float* pred, hipStream_t s, const float* p2w = nullptr);
+    int train_backward(const float* target_nhwc, float upstream, float* loss_dev, hipStream_t s, const float* p2w = nullptr);
+    float* vtarget = nullptr;         // pred_v: the v target of the current step (NHWC), written next to x_t
+    float* obj_rows = nullptr;        // [3][B] device copies of ddif_objective_rows (recon_xt | recon_out | p2_weight)
+    int objective_rows(const ddif_objective_rows* rows, bool need_p2, hipStream_t s);
+    int recon(const float* src_nhwc, float* out, bool nchw, hipStream_t s);  // x0 from x_in and a prediction with obj_rows
     void train_set_stem_source(const float* sc_nhwc);
     int time_rows_aux(const float* t_host, int rows, float* aux, hipStream_t s);
 
@@ -288,17 +297,17 @@ struct Plan {
     int train_random_masks(uint64_t seed, uint64_t tile0, float p_drop, float p_path, hipStream_t s);
     int set_cond(const float* cond, hipStream_t s);
     int forward(const float* x, const float* t_host, const float* sc, float* out, hipStream_t s);
-    int run_sampler(int kind, int n_steps, const float* const* tabs_host, int n_tabs, const float* t_model, const float* xT,
+    int run_sampler(int kind, int n_steps, const float* const* tabs_host, int n_tabs, const ddif_pred_tables* pred_tabs, const float* t_model, const float* xT,
                     const float* noise, uint64_t seed, uint64_t tile0, float lo, float hi, int do_clamp, float* out, hipStream_t s);
     void drop_graphs();
-    int sample_ddpm(const ddif_ddpm_tables* t, const float* xT, const float* noise, uint64_t seed, uint64_t tile0,
+    int sample_ddpm(const ddif_ddpm_tables* t, const ddif_pred_tables* pt, const float* xT, const float* noise, uint64_t seed, uint64_t tile0,
                     float lo, float hi, int do_clamp, float* out, hipStream_t s);
-    int sample_ddim(const ddif_ddim_tables* t, const float* xT, const float* noise, uint64_t seed, uint64_t tile0,
+    int sample_ddim(const ddif_ddim_tables* t, const ddif_pred_tables* pt, const float* xT, const float* noise, uint64_t seed, uint64_t tile0,
                     float lo, float hi, int do_clamp, float* out, hipStream_t s);
     int sample_dpmpp(const ddif_dpm_tables* t, const float* xT, float lo, float hi, int do_clamp, float* out,
                      hipStream_t s);
     int q_sample_forward(const float* x0, const float* noise, const float* a_h, const float* s_h, const float* t_h,
-                         const float* sc, float* pred, hipStream_t s);
+                         const float* sc, float* pred, hipStream_t s, const ddif_objective_rows* rows = nullptr, float* recon_out = nullptr);
 };
 
 }  // namespace ddif

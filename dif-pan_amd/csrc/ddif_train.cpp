@@ -746,14 +746,21 @@ int Plan::build_backward() {
 }
 
 // run after the forward (Plan::train_step, ddif_plan.cpp): loss, its gradient, the reverse program
-int Plan::train_backward(const float* target_nhwc, float upstream, float* loss_dev, hipStream_t s) {
+int Plan::train_backward(const float* target_nhwc, float upstream, float* loss_dev, hipStream_t s, const float* p2w) {
     const size_t n = (size_t)B * H * W * C;
-    {
-        const int nblk = 256;
+    const int nblk = 256;
+    if (loss_type == DDIF_LOSS_L1 && !p2w) {  // the engine's configuration: the launches it always had
         hipLaunchKernelGGL(l1_partial_kernel, dim3(nblk), dim3(256), 256 * sizeof(double), s, (const float*)net_out.p, target_nhwc, n, ts->spart);
         hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(64), 0, s, (const double*)ts->spart, nblk, n, d_loss);
+        tk::l1_bwd(s, net_out.p, target_nhwc, n, upstream, d_net_out);
+    } else {  // MSE and / or p2 weighting: same two-stage fixed-order reduction; d_loss[1] carries the weighting factor to the gradient kernel
+        const int l2 = loss_type == DDIF_LOSS_L2;
+        if (l2) hipLaunchKernelGGL(mse_partial_kernel, dim3(nblk), dim3(256), 256 * sizeof(double), s, (const float*)net_out.p, target_nhwc, n, ts->spart);
+        else hipLaunchKernelGGL(l1_partial_kernel, dim3(nblk), dim3(256), 256 * sizeof(double), s, (const float*)net_out.p, target_nhwc, n, ts->spart);
+        hipLaunchKernelGGL(loss_final_w_kernel, dim3(1), dim3(64), 0, s, (const double*)ts->spart, nblk, n, p2w, B, d_loss);
+        const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+        hipLaunchKernelGGL(loss_bwd_w_kernel, dim3(blocks), dim3(256), 0, s, (const float*)net_out.p, target_nhwc, n, l2, upstream, (const float*)d_loss, d_net_out);
     }
-    tk::l1_bwd(s, net_out.p, target_nhwc, n, upstream, d_net_out);
     for (auto& f : bwd) f(s);
     train_join(s);  // every weight gradient is in place
     if (loss_dev) DDIF_HIPCHK(hipMemcpyAsync(loss_dev, d_loss, sizeof(float), hipMemcpyDeviceToDevice, s));

@@ -121,7 +121,9 @@ struct StageKind {
 // pixel in ONE wave (NB = WN = 1, Cout = 32).  The accumulator layout of D^T = W^T X^T -- lane (j, h) holds couts 8g + 4h + i of pixel j -- IS a B operand of
 // v_mfma_f32_32x32x2_f32 for a contraction over those couts when step s = 4g + i contracts cout 8g + 4h + i (k = h): the K order of a GEMM is free, the x_conv
 // weights are packed in that order, and the 32 x 32 product costs 16 exact-fp32 MFMAs per 32 pixels with no data movement at all.
-enum { EPI_FILM = 1, EPI_SOUT = 2, EPI_RES = 4, EPI_SILU = 8, EPI_TBS = 16, EPI_COLST = 32, EPI_SAMP = 64, EPI_XF1 = 128, EPI_XF2 = 256 };
+// 512 = EPI_PRED (with EPI_SAMP only): the conv output is the noise or v prediction; the epilogue turns it into x0 (sampler_dev.h pred_x0, tables 6 / 7 of the
+// run) in front of the clamp.  A separate instantiation: the x_start sampler kernel keeps its instantiation and arithmetic (its SamplerRun copy is two pointers longer).
+enum { EPI_FILM = 1, EPI_SOUT = 2, EPI_RES = 4, EPI_SILU = 8, EPI_TBS = 16, EPI_COLST = 32, EPI_SAMP = 64, EPI_XF1 = 128, EPI_XF2 = 256, EPI_PRED = 512 };
 // VEC (input staging): 0 = scalar loads, any channel counts;  1 = float4 loads, every CK-channel chunk lies in ONE source
 // (c1 == 0 or c0 % CK == 0): the source base is wave-uniform (SGPR) and a load costs one VALU add;  2 = float4 loads with
 // a per-thread source select (the stem's cat[x, x] with 8 + 8 channels).
@@ -182,6 +184,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
     constexpr bool GNP = (PRO == PRO_GN || PRO == PRO_GN_SILU || PRO == PRO_GN_DW);
     constexpr bool FILM = (EPI & EPI_FILM) != 0, SOUT = (EPI & EPI_SOUT) != 0, RES = (EPI & EPI_RES) != 0, SILU = (EPI & EPI_SILU) != 0, TBS = (EPI & EPI_TBS) != 0;
     constexpr bool SAMP = (EPI & EPI_SAMP) != 0;
+    constexpr bool PRED = (EPI & EPI_PRED) != 0;
+    static_assert(!PRED || SAMP, "prediction conversion: sampler epilogue only");
     constexpr int NBX = (EPI & EPI_XF1) ? 1 : ((EPI & EPI_XF2) ? 2 : 0);  // 32-cout blocks of the folded x_conv
     constexpr bool XF = NBX > 0;
     static_assert(!SAMP || (!SOUT && !RES && !FILM), "sampler epilogue: the plain vector epilogue of the final conv");
@@ -247,7 +251,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
     // sampler epilogue: this step's coefficients (scalar loads, once per workgroup)
     [[maybe_unused]] SamplerRun s_run{};
     [[maybe_unused]] int s_k = 0;
-    [[maybe_unused]] float s_c0 = 0.f, s_c1 = 0.f, s_c2 = 0.f, s_c3 = 0.f, s_c4 = 0.f;
+    [[maybe_unused]] float s_c0 = 0.f, s_c1 = 0.f, s_c2 = 0.f, s_c3 = 0.f, s_c4 = 0.f, s_px = 0.f, s_po = 0.f;
     [[maybe_unused]] const float* s_noise = nullptr;
     if constexpr (SAMP) {
         s_run = *a.s_run;
@@ -258,6 +262,10 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
         if (a.s_kind == 1) {
             s_c3 = s_run.tab[3][s_k];
             s_c4 = s_run.tab[4][s_k];
+        }
+        if constexpr (PRED) {
+            s_px = s_run.tab[6][s_k];
+            s_po = s_run.tab[7][s_k];
         }
         s_noise = s_run.noise ? s_run.noise + (size_t)s_k * ((size_t)a.B * a.Cout * a.Hout * a.Wout) : nullptr;
         if (blockIdx.x == 0 && tid == 0) *a.s_step_next = s_k + 1;  // the next step's kernels read the OTHER counter (nobody reads this one during this step)
@@ -903,6 +911,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
                                         for (int i = 0; i < 4; ++i) {
                                             float x0 = v[i];
                                             const float l = (&e_xl[mb][nb][g].x)[i], xi = (&e_xi[mb][nb][g].x)[i];
+                                            if constexpr (PRED) x0 = pred_x0(s_px, xi, s_po, x0);  // noise / v prediction -> x0 (:369-375)
                                             if (s_run.do_clamp) x0 = fminf(fmaxf(x0 + l, s_run.lo), s_run.hi) - l;
                                             const size_t e = ((size_t)Cp.b * a.Cout + co + i) * hw + pin;  // NCHW element index: the noise layout / Philox key
                                             if (a.s_kind == 0) {

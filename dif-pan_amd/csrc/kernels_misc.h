@@ -778,6 +778,7 @@ struct StepArgs {
     int B, C, HW;
     const SamplerRun* run;
     const int* step;
+    int pred;          // 1: x0 holds the noise / v prediction -> pred_x0 with tables 6 / 7 in front of the clamp (:369-375); 0: x_start
 };
 __global__ void step_advance_kernel(const int* cur, int* next) { *next = *cur + 1; }  // double-buffered counters: nobody reads `next` during this step
 
@@ -788,6 +789,7 @@ __global__ void ddpm_step_kernel(StepArgs a) {
     const SamplerRun r = *a.run;
     const int k = *a.step;
     const float c1 = r.tab[0][k], c2 = r.tab[1][k], c3 = r.tab[2][k];
+    const float px = a.pred ? r.tab[6][k] : 0.f, po = a.pred ? r.tab[7][k] : 0.f;
     const size_t total = (size_t)a.B * a.HW * a.C;
     const float* noise = r.noise ? r.noise + (size_t)k * total : nullptr;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -795,6 +797,7 @@ __global__ void ddpm_step_kernel(StepArgs a) {
         const size_t p = (i / a.C) % a.HW;
         const size_t b = i / ((size_t)a.C * a.HW);
         float x0 = a.x0[i];
+        if (a.pred) x0 = pred_x0(px, a.img[i], po, x0);
         if (r.do_clamp) {
             const float l = a.lms[i];
             x0 = fminf(fmaxf(x0 + l, r.lo), r.hi) - l;
@@ -813,6 +816,7 @@ __global__ void ddim_step_kernel(StepArgs a) {
     const SamplerRun r = *a.run;
     const int k = *a.step;
     const float sqrt_recip = r.tab[0][k], sqrt_recipm1 = r.tab[1][k], sqrt_ap = r.tab[2][k], dir_coef = r.tab[3][k], sigma = r.tab[4][k];
+    const float px = a.pred ? r.tab[6][k] : 0.f, po = a.pred ? r.tab[7][k] : 0.f;
     const size_t total = (size_t)a.B * a.HW * a.C;
     const float* noise = r.noise ? r.noise + (size_t)k * total : nullptr;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -820,11 +824,12 @@ __global__ void ddim_step_kernel(StepArgs a) {
         const size_t p = (i / a.C) % a.HW;
         const size_t b = i / ((size_t)a.C * a.HW);
         float x0 = a.x0[i];
+        const float img = a.img[i];
+        if (a.pred) x0 = pred_x0(px, img, po, x0);  // eps below is recomputed from this x0, as the reference does (:605-606)
         if (r.do_clamp) {
             const float l = a.lms[i];
             x0 = fminf(fmaxf(x0 + l, r.lo), r.hi) - l;
         }
-        const float img = a.img[i];
         const float eps = (sqrt_recip * img - x0) / sqrt_recipm1;
         float v = x0 * sqrt_ap + dir_coef * eps;
         if (sigma != 0.f) {
@@ -838,12 +843,19 @@ __global__ void ddim_step_kernel(StepArgs a) {
 
 // DPM-Solver++ data prediction (solver/dpm_solver.py:298-300,441-450): the x_start -> eps -> x_start round trip of
 // model_wrapper + data_prediction_fn, then the image-space clamp corrector (diffusion_engine.py:43-49).
+// model_type (solver/dpm_solver.py:296-303; the plan's pred_mode): 0 "x_start" eps = (x - alpha o) / sigma, 1 "noise" eps = o, 2 "v" eps = alpha o + sigma x.
 __global__ void dpm_x0_kernel(const float* net, const float* x, const float* lms, float alpha, float sigma, float lo,
-                              float hi, int do_clamp, size_t total, float* x0_out) {
+                              float hi, int do_clamp, int model_type, size_t total, float* x0_out) {
 #pragma clang fp contract(off)
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const float xv = x[i];
-        const float eps = (xv - alpha * net[i]) / sigma;
+        const float xv = x[i], o = net[i];
+        float eps;
+        if (model_type == 0) eps = (xv - alpha * o) / sigma;
+        else if (model_type == 1) eps = o;
+        else {
+            const float p = alpha * o, q = sigma * xv;
+            eps = p + q;
+        }
         float x0 = (xv - sigma * eps) / alpha;
         if (do_clamp) {
             const float l = lms[i];
@@ -886,6 +898,32 @@ __global__ void dpm_update_kernel(DpmUpdArgs a) {
     }
 }
 
+// x0 from a prediction, per-sample coefficients (p_losses :708-713 self-conditioning pass, :724 / :735 recon_x0): out = cx[b]*x_t - co[b]*o, NHWC in,
+// NCHW out when `nchw` (the boundary layout) else NHWC
+__global__ void recon_x0_kernel(const float* xt, const float* o, const float* cx, const float* co, int B, int C, int HW, int nchw, float* out) {
+#pragma clang fp contract(off)
+    const size_t total = (size_t)B * HW * C;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C);
+        const size_t p = (i / C) % HW;
+        const size_t b = i / ((size_t)C * HW);
+        const float v = pred_x0(cx[b], xt[i], co[b], o[i]);
+        out[nchw ? (b * C + c) * HW + p : i] = v;
+    }
+}
+// q_sample + the v target of the same sample (:304-308 predict_v_from_start): v = a[b]*noise - s[b]*x0, written by the pass that writes x_t
+__global__ void q_sample_v_kernel(const float* x0, const float* noise, const float* a, const float* s, int B, size_t per, float* out, float* v_out) {
+#pragma clang fp contract(off)
+    const size_t total = (size_t)B * per;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = i / per;
+        const float av = a[b], sv = s[b], x = x0[i], z = noise[i];
+        const float p0 = av * x, p1 = sv * z;
+        out[i] = p0 + p1;
+        const float q0 = av * z, q1 = sv * x;
+        v_out[i] = q0 - q1;
+    }
+}
 // q_sample (:668-681): x_t = a[b]*x0 + s[b]*noise, all NHWC
 __global__ void q_sample_kernel(const float* x0, const float* noise, const float* a, const float* s, int B, size_t per,
                                 float* out) {

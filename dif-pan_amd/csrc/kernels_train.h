@@ -366,6 +366,57 @@ __global__ void l1_final_kernel(const double* part, int nblk, size_t n, float* o
         out[0] = (float)(s / (double)n);
     }
 }
+// F.mse_loss(pred, target), mean (nn.MSELoss, diffusion_ddpm_pan.py:154-155): the same two stages on squared differences
+__global__ __launch_bounds__(256) void mse_partial_kernel(const float* pred, const float* target, size_t n, double* part) {
+    DDIF_DYN_SMEM(smem_);
+    double* red = reinterpret_cast<double*>(smem_);
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    for (size_t i = (size_t)blockIdx.x * 256 + tid; i < n; i += (size_t)gridDim.x * 256) {
+        const float d = pred[i] - target[i];
+        s += (double)d * (double)d;
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int st = 128; st >= 1; st >>= 1) {
+        if (tid < st) red[tid] += red[tid + st];
+        __syncthreads();
+    }
+    if (tid == 0) part[blockIdx.x] = red[0];
+}
+// final sum of either loss + the p2 weighting (:762-764): `loss` is a scalar there, so the reference computes mean_b(loss * w[b]) with w[b] = p2_loss_weight[t_b];
+// out[0] = that value, out[1] = mean_b(w[b]) = d out[0] / d loss, the factor the gradient kernel below multiplies by.  w null: out[0] = loss, out[1] = 1.
+__global__ void loss_final_w_kernel(const double* part, int nblk, size_t n, const float* w, int B, float* out) {
+#pragma clang fp contract(off)
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        double s = 0.0;
+        for (int k = 0; k < nblk; ++k) s += part[k];
+        const float loss = (float)(s / (double)n);
+        if (!w) {
+            out[0] = loss;
+            out[1] = 1.f;
+        } else {
+            float acc = 0.f, wsum = 0.f;
+            for (int b = 0; b < B; ++b) {
+                acc += loss * w[b];
+                wsum += w[b];
+            }
+            out[0] = acc / (float)B;
+            out[1] = wsum / (float)B;
+        }
+    }
+}
+// d loss / d pred for either loss, scaled by upstream * scale[1] (scale: the two floats loss_final_w_kernel wrote):
+//   L1: sign(pred - target) / n (torch: sign(0) = 0);  MSE: (2 / n) (pred - target)
+__global__ void loss_bwd_w_kernel(const float* pred, const float* target, size_t n, int l2, float upstream, const float* scale, float* dpred) {
+#pragma clang fp contract(off)
+    const float up = upstream * scale[1];
+    const float g = up / (float)n, norm = 2.0f / (float)n;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float df = pred[i] - target[i];
+        dpred[i] = l2 ? (norm * df) * up : (df > 0.f ? g : (df < 0.f ? -g : 0.f));
+    }
+}
 // time MLP, top layer: dte[b][k] = sum_o dtb[b][o] wall[o][k]  (o over all 2272 FeatureWiseAffine outputs).  One workgroup per sample; thread
 // (group g = tid / inner, k = tid % inner) sums the outputs o = g, g + G, ...; the G partials are added in group order
 __global__ __launch_bounds__(256) void time_dte_kernel(const float* dtb, const float* wall, int ns, int inner, float* dte) {

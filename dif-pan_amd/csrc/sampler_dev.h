@@ -10,8 +10,18 @@ struct SamplerRun {
     unsigned long long seed, tile0;
     float lo, hi;
     int do_clamp, n_steps;
-    const float* tab[6];  // per-step coefficient tables (device), meaning depends on the sampler
+    const float* tab[8];  // per-step coefficient tables (device), meaning depends on the sampler: [0, 6) the update's, [6, 8) the prediction's (pred_x0)
 };
+
+// Network output o -> x0 for the noise / v parameterisations (diffusion_ddpm_pan.py:298-302 predict_start_from_noise, :310-314 predict_start_from_v):
+// both are  cx * x_t - co * o  in the reference's operand order, with (cx, co) = (sqrt_recip_alphas_cumprod[t], sqrt_recipm1_alphas_cumprod[t]) for
+// "noise" and (sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]) for "pred_v"; the caller hands over the pair that belongs to its mode.
+// Two roundings of the products, one of the difference: no contraction.
+__device__ __forceinline__ float pred_x0(float cx, float xt, float co, float o) {
+#pragma clang fp contract(off)
+    const float p = cx * xt, q = co * o;
+    return p - q;
+}
 
 // ----------------------------------------------------------------------------------------------------------------
 // counter-based normal generator (Philox4x32-10 + Box-Muller), keyed by (seed, draw index, global element index) so

@@ -6,8 +6,9 @@ loops do not run in Python: `p_sample_loop` / `ddim_sample_loop` hand the per-st
 (`ddif_plan_sample_ddpm` / `ddif_plan_sample_ddim`, include/ddif.h), which enqueues the whole T-step loop of
 hand-written gfx950 kernels on the current stream.
 
-Implemented: conditional models, pred_mode="x_start", clamp_type="abs", loss "l1"/"l2" (forward value only --
-the backward pass of config 5 is not built yet).  Everything else raises; there is no fallback.
+Implemented: conditional models, pred_mode "x_start" / "noise" / "pred_v" (samplers, p_losses, the native training step),
+clamp_type="abs", loss "l1" / "l2" (value and backward pass), p2 loss weighting.  Still refused (DdifError, no fallback):
+unconditional models, clamp_type="dynamic", loss_type="l1ssim", get_interm_fm.
 """
 from __future__ import annotations
 
@@ -68,8 +69,8 @@ class _NativeTrainFn(torch.autograd.Function):
     to the plan and are overwritten by the next step: torch accumulates them into `.grad` right away, as the reference's autograd does."""
 
     @staticmethod
-    def forward(ctx, plan, x_start, noise, a, s, t, x_self_cond, gbuf, *params):
-        loss, pred = plan.train_step(x_start, noise, a, s, t, x_self_cond)
+    def forward(ctx, plan, x_start, noise, a, s, t, x_self_cond, gbuf, rows, *params):
+        loss, pred = plan.train_step(x_start, noise, a, s, t, x_self_cond, **({} if rows is None else {"rows": rows}))  # (no rows: the engine's call, unchanged)
         flat, views, offs = gbuf
         ctx.snapshot = flat.clone()  # the plan's buffer is overwritten by the next step; this copy is what backward() hands out
         ctx.meta = (offs, [v.shape for v in views])
@@ -82,7 +83,7 @@ class _NativeTrainFn(torch.autograd.Function):
         if float(gloss) != 1.0:
             flat = flat * gloss
         offs, shapes = ctx.meta
-        return (None,) * 8 + tuple(flat[o:o + int(torch.Size(sh).numel())].view(sh) for o, sh in zip(offs, shapes))
+        return (None,) * 9 + tuple(flat[o:o + int(torch.Size(sh).numel())].view(sh) for o, sh in zip(offs, shapes))
 
 
 class GaussianDiffusion(nn.Module):
@@ -165,14 +166,43 @@ class GaussianDiffusion(nn.Module):
     def _plan(self, cond: torch.Tensor, train: bool = False):
         if not self.conditional:
             raise DdifError("unconditional sampling is not implemented by the HIP path")
-        if self.pred_mode != "x_start":
-            raise DdifError(f"pred_mode='{self.pred_mode}' is not implemented by the HIP path (the engine uses 'x_start')")
         if self.clamp_type != "abs":
             raise DdifError("clamp_type='dynamic' is not implemented by the HIP path")
         B, _, H, W = cond.shape
         plan = self.model.plan_for(B, H, W, cond.device, train=train)
+        plan.set_objective(self.pred_mode, self.loss_type)  # sticky on the (cached) plan: every entry below states it
         plan.set_cond(cond)
         return plan
+
+    def _pred_buffers(self):
+        """The schedule pair (cx, co) of x0 = cx[t] * x_t - co[t] * out for this pred_mode (reference :298-302, :310-314); None for x_start."""
+        if self.pred_mode == "noise":
+            return self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod
+        if self.pred_mode == "pred_v":
+            return self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod
+        return None
+
+    def _pred_tables(self, order):
+        pb = self._pred_buffers()
+        if pb is None:
+            return None
+        cx, co = pb[0].detach().cpu(), pb[1].detach().cpu()
+        return [float(cx[i]) for i in order], [float(co[i]) for i in order]
+
+    def _objective_rows(self, t, p2=True):
+        """Per-sample rows of the library's p_losses entry points: the pred pair gathered at t and p2_loss_weight[t] (None when gamma == 0, where
+        the weights are exactly 1)."""
+        pb = self._pred_buffers()
+        w = None
+        if p2 and float(self.p2_loss_weight_gamma) != 0.0:
+            tab = self.p2_loss_weight.detach()
+            w = (tab if tab.device == t.device else tab.to(t.device))[t]
+        if pb is None and w is None:
+            return None
+        cx = co = None
+        if pb is not None:
+            cx, co = [(b.detach() if b.device == t.device else b.detach().to(t.device))[t] for b in pb]
+        return cx, co, w
 
     @staticmethod
     def _seed_from_torch() -> int:
@@ -182,6 +212,18 @@ class GaussianDiffusion(nn.Module):
         noise = default(noise, lambda: torch.randn_like(x_start))
         return (extract(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
                 + extract(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * noise)
+
+    def predict_start_from_noise(self, x_t, t, noise):
+        return (extract(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t
+                - extract(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape) * noise)
+
+    def predict_v_from_start(self, x_start, t, noise):
+        return (extract(self.sqrt_alphas_cumprod, t, x_start.shape) * noise
+                - extract(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * x_start)
+
+    def predict_start_from_v(self, x_t, t, v):
+        return (extract(self.sqrt_alphas_cumprod, t, x_t.shape) * x_t
+                - extract(self.sqrt_one_minus_alphas_cumprod, t, x_t.shape) * v)
 
     def predict_noise_from_start(self, x_t, t, x_0_pred):
         return ((extract(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t - x_0_pred)
@@ -217,6 +259,8 @@ class GaussianDiffusion(nn.Module):
         cx0 = [float(c1[i]) for i in order]
         cxt = [float(c2[i]) for i in order]
         czz = [0.0 if i == 0 else float(cz[i]) for i in order]
+        ptab = self._pred_tables(order)
+        pseg = (lambda sl: None) if ptab is None else (lambda sl: (ptab[0][sl], ptab[1][sl]))
         if x_T is None and not device_rng:
             x_T = torch.randn((B, self.channels, H, W), device=dev)
         if noise is None and seed is None:
@@ -225,7 +269,7 @@ class GaussianDiffusion(nn.Module):
         if continous and x_T is None:
             raise DdifError("continous=True needs an explicit or torch-drawn x_T (device_rng=False)")
         if not continous:
-            return plan.sample_ddpm(t_model, cx0, cxt, czz, x_T, noise, seed, tile0, clamp, dev)
+            return plan.sample_ddpm(t_model, cx0, cxt, czz, x_T, noise, seed, tile0, clamp, dev, pred=ptab)
         # continous=True: snapshots whenever i % sample_inter == 0 (:448,500-501) -> run the loop in segments
         sample_inter = 1 | (T // 10)
         ret, img, start = x_T, x_T, 0
@@ -233,7 +277,7 @@ class GaussianDiffusion(nn.Module):
             if i % sample_inter == 0:
                 seg = slice(start, k + 1)
                 nz = None if noise is None else noise[seg]
-                img = plan.sample_ddpm(t_model[seg], cx0[seg], cxt[seg], czz[seg], img, nz, seed + start, tile0, clamp, dev)
+                img = plan.sample_ddpm(t_model[seg], cx0[seg], cxt[seg], czz[seg], img, nz, seed + start, tile0, clamp, dev, pred=pseg(seg))
                 ret = torch.cat([ret, img], dim=0)
                 start = k + 1
         return ret
@@ -303,7 +347,8 @@ class GaussianDiffusion(nn.Module):
         return plan.sample_ddim(
             [float(j) for j in order], [float(sr[j]) for j in order], [float(srm1[j]) for j in order],
             [float(sqrt_ap[j]) for j in order], [float(dirc[j]) for j in order],
-            [0.0 if j == 0 else float(sigma[j]) for j in order], x_T, noise, 0 if seed is None else seed, tile0, clamp, dev)
+            [0.0 if j == 0 else float(sigma[j]) for j in order], x_T, noise, 0 if seed is None else seed, tile0, clamp, dev,
+            pred=self._pred_tables(order))
 
     # ------------------------------------------------------------------------------------------------ training
     def _schedule_rows(self, t):
@@ -323,8 +368,8 @@ class GaussianDiffusion(nn.Module):
         b = x_start.shape[0]
         t = torch.randint(0, self.num_timesteps, (b,), device=x_start.device).long()
         noise = default(noise, lambda: torch.randn_like(x_start))
-        if self.pred_mode != "x_start" or not self.conditional:
-            raise DdifError("p_losses: only conditional pred_mode='x_start' is implemented by the HIP path")
+        if not self.conditional:
+            raise DdifError("p_losses: unconditional models are not implemented by the HIP path")
         training = bool(getattr(self.model, "training", False))
         plan = self._plan(cond, train=training)
 
@@ -338,17 +383,30 @@ class GaussianDiffusion(nn.Module):
                 plan.random_train_masks(self._seed_from_torch(), 0, float(self.model.cfg["dropout"]), self.model.DROP_PATH_PROB)
 
         a, s = self._schedule_rows(t)
+        native = self.pred_mode == "x_start"
+        rec_rows = self._objective_rows(t, p2=False)
         x_self_cond = None
         if self.self_condition and random.random() < 0.5:
             masks()
-            x_self_cond = plan.q_sample_forward(x_start, noise, a, s, t, None)  # no-grad pass of the reference (:703-709)
+            # no-grad pass of the reference (:703-714): the x0 rebuilt from the prediction
+            x_self_cond = plan.q_sample_forward(x_start, noise, a, s, t, None, rows=rec_rows, want="pred" if native else "recon")
         if training and torch.is_grad_enabled():
             return self._train_step(x_start, noise, a, s, t, cond, x_self_cond)
         masks()
         pred = plan.q_sample_forward(x_start, noise, a, s, t, x_self_cond)
-        loss = self.loss_func(x_start, pred)
+        # loss value and recon_x0 of the evaluation path (:722-736, 762-764), on the prediction the kernels returned
+        if self.pred_mode == "noise":
+            recon = self.predict_start_from_noise(self.q_sample(x_start, t, noise), t, pred)
+            loss = self.loss_func(noise, pred)
+        elif self.pred_mode == "pred_v":
+            v = self.predict_v_from_start(x_start, t, noise)
+            recon = self.predict_start_from_v(self.q_sample(x_start, t, noise), t, v)  # from the TRUE v, as the reference does (:734-735)
+            loss = self.loss_func(v, pred)
+        else:
+            recon = pred
+            loss = self.loss_func(x_start, pred)
         loss = (loss * extract(self.p2_loss_weight, t, loss.shape)).mean()
-        return loss, pred
+        return loss, recon
 
     def _train_step(self, x_start, noise, a, s, t, cond, x_self_cond):
         """The differentiable pass of p_losses (:711-766) as ONE library call: q_sample, the train-mode forward over NHWC activations, the L1
@@ -358,13 +416,10 @@ class GaussianDiffusion(nn.Module):
         masks come from the library's counter-based generator keyed by (seed, site, GLOBAL tile index `self.train_tile0 + b`, element) --
         so a batch split over ranks draws the masks the unsplit batch would -- or are the ones pinned with `model.set_train_masks`.
         (Round 2's op-by-op Python tape is test scaffolding: tests/train_tape.py `tape_train_step`, which the cross-check test patches in for `_train_step`.)"""
-        if self.loss_type != "l1":
-            raise DdifError("training: only loss_type='l1' (the engine configuration) has a backward pass")
-        if float(getattr(self, "p2_loss_weight_gamma", 0.0)) != 0.0:
-            raise DdifError("training: p2 loss weighting is not implemented by the backward pass")
         model = self.model
         named = model.named_parameter_list() if hasattr(model, "named_parameter_list") else [(n, p) for n, p in model.named_parameters()]
         plan = self._native_plan(x_start, cond, named)
+        rows = self._objective_rows(t)
         gb = getattr(plan, "_grad_bufs", None)
         if gb is None:
             # one flat buffer, one 64-float-aligned view per parameter: backward() hands torch a single clone of it
@@ -377,13 +432,14 @@ class GaussianDiffusion(nn.Module):
             gb = plan._grad_bufs = (flat, views, offs)
             plan._bound_ptrs = None
         self._bind(plan, named, gb[1])
-        loss, pred = _NativeTrainFn.apply(plan, x_start, noise, a, s, t, x_self_cond, gb, *[p for _, p in named])
+        loss, pred = _NativeTrainFn.apply(plan, x_start, noise, a, s, t, x_self_cond, gb, rows, *[p for _, p in named])
         return loss, pred
 
     def _native_plan(self, x_start, cond, named):
         model = self.model
         B, _, H, W = x_start.shape
         plan = model.plan_for(B, H, W, x_start.device, train=True)
+        plan.set_objective(self.pred_mode, self.loss_type)
         if not getattr(model._net, "device_refreshed", False):
             model._net.refresh_from_device(named)  # first use after a host commit: fills the dgrad packs
         plan.set_cond(cond)
@@ -413,8 +469,6 @@ class GaussianDiffusion(nn.Module):
         """p_losses + loss.backward() of the reference (:692-766, diffusion_engine.py:230-233) with the gradients WRITTEN straight into `grads`
         (one contiguous fp32 tensor per parameter, `model.parameters()` order) -- what `engine_google` hands to its fused optimizer; no
         autograd node, no per-parameter accumulation launches.  Same random draws, in the same order, as p_losses.  Returns (loss, recon)."""
-        if self.loss_type != "l1" or float(getattr(self, "p2_loss_weight_gamma", 0.0)) != 0.0:
-            raise DdifError("training: only loss_type='l1' without p2 weighting has a backward pass")
         model = self.model
         if not getattr(model, "training", False):
             raise DdifError("train_step_into needs the model in .train() mode")
@@ -426,10 +480,13 @@ class GaussianDiffusion(nn.Module):
         x_self_cond = None
         if self.self_condition and random.random() < 0.5:
             plan = self._native_plan(x_start, cond, named)
-            x_self_cond = plan.q_sample_forward(x_start, noise, a, s, t, None)  # no-grad pass of the reference (:703-709), its own masks
+            # no-grad pass of the reference (:703-714), its own masks
+            x_self_cond = plan.q_sample_forward(x_start, noise, a, s, t, None, rows=self._objective_rows(t, p2=False),
+                                                want="pred" if self.pred_mode == "x_start" else "recon")
         plan = self._native_plan(x_start, cond, named)
         self._bind(plan, named, grads)
-        return plan.train_step(x_start, noise, a, s, t, x_self_cond)
+        rows = self._objective_rows(t)
+        return plan.train_step(x_start, noise, a, s, t, x_self_cond, **({} if rows is None else {"rows": rows}))
 
     def forward(self, x, mode="train", *args, **kwargs):
         if mode == "train":

@@ -51,6 +51,18 @@ class DpmTables(C.Structure):
                 ("inv_r01", _FP), ("a_phi2", _FP), ("a_phi3", _FP)]
 
 
+class PredTables(C.Structure):
+    _fields_ = [("n_steps", C.c_int32), ("coef_xt", _FP), ("coef_out", _FP)]
+
+
+class ObjectiveRows(C.Structure):
+    _fields_ = [("recon_xt", C.c_void_p), ("recon_out", C.c_void_p), ("p2_weight", C.c_void_p)]
+
+
+PRED_MODES = {"x_start": 0, "noise": 1, "pred_v": 2, "v": 2}  # GaussianDiffusion's names + model_wrapper's "v" (include/ddif.h DDIF_PRED_*)
+LOSS_TYPES = {"l1": 0, "l2": 1}
+
+
 class ProfResult(C.Structure):
     _fields_ = [("launches", C.c_int64), ("total_ms", C.c_double), ("total_flop", C.c_double),
                 ("total_bytes", C.c_double), ("kernel_name", C.c_char * 128), ("steps_recorded", C.c_int64),
@@ -105,6 +117,12 @@ class _Lib:
         d.ddif_plan_sample_ddim.argtypes = [vp, C.POINTER(DdimTables), vp, vp, u64, u64, f32, f32, i32, vp, vp]
         d.ddif_plan_sample_dpmpp.argtypes = [vp, C.POINTER(DpmTables), vp, f32, f32, i32, vp, vp]
         d.ddif_plan_q_sample_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        d.ddif_plan_set_objective.argtypes = [vp, i32, i32]
+        d.ddif_plan_get_objective.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+        d.ddif_plan_sample_ddpm_ex.argtypes = [vp, C.POINTER(DdpmTables), C.POINTER(PredTables), vp, vp, u64, u64, f32, f32, i32, vp, vp]
+        d.ddif_plan_sample_ddim_ex.argtypes = [vp, C.POINTER(DdimTables), C.POINTER(PredTables), vp, vp, u64, u64, f32, f32, i32, vp, vp]
+        d.ddif_plan_q_sample_forward_ex.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(ObjectiveRows), vp, vp, vp]
+        d.ddif_plan_train_step_ex.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(ObjectiveRows), vp, vp, vp, vp]
         d.ddif_prof_begin.argtypes = [vp, i32, i32]
         d.ddif_prof_collect.argtypes = [vp, C.POINTER(ProfResult)]
         d.ddif_prof_classes.argtypes = [vp, C.POINTER(ProfClass)]
@@ -358,6 +376,7 @@ class PlanHandle:
         self._cond_ref = None
         self._cond_ver = None
         self.net_out_channels = net.out_channel
+        self.objective = ("x_start", "l1")
 
     def _create(self):
         h = C.c_void_p()
@@ -375,6 +394,34 @@ class PlanHandle:
                 if prev_mode != self.math_mode:
                     set_math_mode(prev_mode)
         self.h = h
+        obj = getattr(self, "objective", ("x_start", "l1"))
+        if obj != ("x_start", "l1"):  # a rebuilt plan (range fallback) keeps its objective
+            self.objective = ("x_start", "l1")
+            self.set_objective(*obj)
+
+    def set_objective(self, pred_mode: str = "x_start", loss_type: str = "l1"):
+        """What the network output means to the samplers / p_losses and which loss the training step takes (include/ddif.h
+        ddif_plan_set_objective; sticky).  pred_mode: "x_start" | "noise" | "pred_v" (alias "v"), loss_type: "l1" | "l2"."""
+        if pred_mode not in PRED_MODES or loss_type not in LOSS_TYPES:
+            raise DdifError(f"objective ({pred_mode!r}, {loss_type!r}): pred_mode in {sorted(PRED_MODES)}, loss_type in {sorted(LOSS_TYPES)}")
+        obj = ("pred_v" if pred_mode == "v" else pred_mode, loss_type)
+        if obj != self.objective:
+            self.lib.check(self.lib.dll.ddif_plan_set_objective(self.h, PRED_MODES[obj[0]], LOSS_TYPES[obj[1]]), "ddif_plan_set_objective")
+            self.objective = obj
+
+    def get_objective(self):
+        """(pred_mode, loss_type) as the LIBRARY holds them for this plan (include/ddif.h ddif_plan_get_objective)."""
+        a, b = C.c_int(), C.c_int()
+        self.lib.check(self.lib.dll.ddif_plan_get_objective(self.h, C.byref(a), C.byref(b)), "ddif_plan_get_objective")
+        return ({0: "x_start", 1: "noise", 2: "pred_v"}[a.value], {0: "l1", 1: "l2"}[b.value])
+
+    def _objective_rows(self, rows, device):
+        """ObjectiveRows from (recon_xt, recon_out, p2_weight) tensors (each nullable); returns (struct or None, keep-alive list)."""
+        if rows is None:
+            return None, []
+        keep = [None if r is None else _row(r, device) for r in rows]
+        st = ObjectiveRows(*[None if r is None else C.c_void_p(r.data_ptr()) for r in keep])
+        return st, keep
 
     def _range_overflow(self, device) -> bool:
         """ONE synchronisation + 4-byte read per sampler / forward call (never inside a loop): did a conv of this plan stage a value outside the scaled
@@ -486,9 +533,10 @@ class PlanHandle:
         self.lib.check(self.lib.dll.ddif_plan_train_bind(self.h, n, keys, ptrs), "ddif_plan_train_bind")
         self._grads_keep = [t for _, t in named_grads]
 
-    def train_step(self, x0, noise, a, s, time, self_cond, want_pred=True):
-        """One iteration's device work: q_sample, train-mode forward, L1 loss, backward (gradients -> the bound tensors).
-        Returns (loss: 0-d device tensor, pred or None)."""
+    def train_step(self, x0, noise, a, s, time, self_cond, want_pred=True, rows=None):
+        """One iteration's device work: q_sample, train-mode forward, the loss of the plan's objective, backward (gradients -> the bound tensors).
+        Returns (loss: 0-d device tensor, recon_x0 or None).  rows = (recon_xt, recon_out, p2_weight) per-sample rows (each nullable): needed for a
+        noise / v prediction and for p2 weighting (include/ddif.h ddif_objective_rows); without them this is the engine's x_start / L1 step."""
         img = (self.B, self.net.out_channel, self.H, self.W)
         for nm, t in (("x_start", x0), ("noise", noise)) + ((("self_cond", self_cond),) if self_cond is not None else ()):
             _check_tensor(self.lib, t, nm)
@@ -498,6 +546,12 @@ class PlanHandle:
         a, s, t = _row(a, x0.device), _row(s, x0.device), _row(time, x0.device)
         loss = torch.empty((), dtype=torch.float32, device=x0.device)
         pred = torch.empty_like(x0) if want_pred else None
+        if rows is not None or self.objective[0] != "x_start":
+            rst, rkeep = self._objective_rows(rows, x0.device)
+            self.lib.check(self.lib.dll.ddif_plan_train_step_ex(
+                self.h, _ptr(x0), _ptr(noise), C.c_void_p(a.data_ptr()), C.c_void_p(s.data_ptr()), C.c_void_p(t.data_ptr()), _ptr(sc),
+                None if rst is None else C.byref(rst), _ptr(loss), None, _ptr(pred), _stream(self.lib, x0.device)), "ddif_plan_train_step_ex")
+            return loss, pred
         self.lib.check(self.lib.dll.ddif_plan_train_step(
             self.h, _ptr(x0), _ptr(noise), C.c_void_p(a.data_ptr()), C.c_void_p(s.data_ptr()), C.c_void_p(t.data_ptr()), _ptr(sc), _ptr(loss), _ptr(pred),
             _stream(self.lib, x0.device)), "ddif_plan_train_step")
@@ -567,16 +621,33 @@ class PlanHandle:
                 raise DdifError(f"noise: expected shape (>={n_steps},) + {img}, got {tuple(noise.shape)}")
 
     # -- samplers -----------------------------------------------------------------------------------------------
-    def sample_ddpm(self, t_model, c_x0, c_xt, c_z, x_T, noise, seed, tile0, clamp, device) -> torch.Tensor:
+    def _pred_tables(self, pred, n):
+        """PredTables from (coef_xt, coef_out) lists -- required when the plan predicts noise / v, refused otherwise."""
+        if (pred is None) != (self.objective[0] == "x_start"):
+            raise DdifError(f"pred tables {'given' if pred is not None else 'missing'} for a plan whose objective is {self.objective[0]!r}")
+        if pred is None:
+            return None, None
+        keep = [_farr(pred[0]), _farr(pred[1])]
+        if len(keep[0]) != n or len(keep[1]) != n:
+            raise DdifError(f"pred tables: expected {n} steps")
+        return PredTables(n, *[C.cast(a, _FP) for a in keep]), keep
+
+    def sample_ddpm(self, t_model, c_x0, c_xt, c_z, x_T, noise, seed, tile0, clamp, device, pred=None) -> torch.Tensor:
         n = len(t_model)
         keep = [_farr(t_model), _farr(c_x0), _farr(c_xt), _farr(c_z)]
         tabs = DdpmTables(n, *[C.cast(a, _FP) for a in keep])
+        ptabs, pkeep = self._pred_tables(pred, n)
         self._check_sampler_inputs(x_T, noise, n)
         x_T = None if x_T is None else x_T.contiguous()
         noise = None if noise is None else noise.contiguous()
         out = torch.empty((self.B, self.net_out_channels, self.H, self.W), dtype=torch.float32, device=device)
         lo, hi, do = (clamp[0], clamp[1], 1) if clamp is not None else (0.0, 0.0, 0)
         def run():
+            if ptabs is not None:
+                self.lib.check(self.lib.dll.ddif_plan_sample_ddpm_ex(self.h, C.byref(tabs), C.byref(ptabs), _ptr(x_T), _ptr(noise), int(seed),
+                                                                     int(tile0), lo, hi, do, _ptr(out),
+                                                                     _stream(self.lib, torch.device(device))), "ddif_plan_sample_ddpm_ex")
+                return out
             self.lib.check(self.lib.dll.ddif_plan_sample_ddpm(self.h, C.byref(tabs), _ptr(x_T), _ptr(noise), int(seed),
                                                               int(tile0), lo, hi, do, _ptr(out),
                                                               _stream(self.lib, torch.device(device))), "ddif_plan_sample_ddpm")
@@ -585,16 +656,22 @@ class PlanHandle:
         return self._guarded(run, device)
 
     def sample_ddim(self, t_model, sqrt_recip, sqrt_recipm1, sqrt_ap, dir_coef, sigma, x_T, noise, seed, tile0, clamp,
-                    device) -> torch.Tensor:
+                    device, pred=None) -> torch.Tensor:
         n = len(t_model)
         keep = [_farr(v) for v in (t_model, sqrt_recip, sqrt_recipm1, sqrt_ap, dir_coef, sigma)]
         tabs = DdimTables(n, *[C.cast(a, _FP) for a in keep])
+        ptabs, pkeep = self._pred_tables(pred, n)
         self._check_sampler_inputs(x_T, noise, n)
         x_T = None if x_T is None else x_T.contiguous()
         noise = None if noise is None else noise.contiguous()
         out = torch.empty((self.B, self.net_out_channels, self.H, self.W), dtype=torch.float32, device=device)
         lo, hi, do = (clamp[0], clamp[1], 1) if clamp is not None else (0.0, 0.0, 0)
         def run():
+            if ptabs is not None:
+                self.lib.check(self.lib.dll.ddif_plan_sample_ddim_ex(self.h, C.byref(tabs), C.byref(ptabs), _ptr(x_T), _ptr(noise), int(seed),
+                                                                     int(tile0), lo, hi, do, _ptr(out),
+                                                                     _stream(self.lib, torch.device(device))), "ddif_plan_sample_ddim_ex")
+                return out
             self.lib.check(self.lib.dll.ddif_plan_sample_ddim(self.h, C.byref(tabs), _ptr(x_T), _ptr(noise), int(seed),
                                                               int(tile0), lo, hi, do, _ptr(out),
                                                               _stream(self.lib, torch.device(device))), "ddif_plan_sample_ddim")
@@ -619,7 +696,9 @@ class PlanHandle:
 
         return self._guarded(run, x_T.device)
 
-    def q_sample_forward(self, x0, noise, a, s, time, self_cond) -> torch.Tensor:
+    def q_sample_forward(self, x0, noise, a, s, time, self_cond, rows=None, want="pred") -> torch.Tensor:
+        """want="pred": the raw network output; want="recon": the x0 rebuilt from it under the plan's objective (rows = (recon_xt, recon_out, None):
+        the schedule pair of the mode gathered at t) -- what p_losses' self-conditioning pass feeds back."""
         img = (self.B, self.net.out_channel, self.H, self.W)
         for nm, t in (("x_start", x0), ("noise", noise)) + ((("self_cond", self_cond),) if self_cond is not None else ()):
             _check_tensor(self.lib, t, nm)
@@ -628,7 +707,14 @@ class PlanHandle:
         sc = None if self_cond is None else self_cond.contiguous()
         a, s, t = _row(a, x0.device), _row(s, x0.device), _row(time, x0.device)
         out = torch.empty_like(x0)
+        rst, rkeep = self._objective_rows(rows, x0.device)
         def run():
+            if self.objective[0] != "x_start" or want == "recon":
+                self.lib.check(self.lib.dll.ddif_plan_q_sample_forward_ex(
+                    self.h, _ptr(x0), _ptr(noise), C.c_void_p(a.data_ptr()), C.c_void_p(s.data_ptr()), C.c_void_p(t.data_ptr()),
+                    _ptr(sc), None if rst is None else C.byref(rst), _ptr(out) if want == "pred" else None, _ptr(out) if want == "recon" else None,
+                    _stream(self.lib, x0.device)), "ddif_plan_q_sample_forward_ex")
+                return out
             self.lib.check(self.lib.dll.ddif_plan_q_sample_forward(
                 self.h, _ptr(x0), _ptr(noise), C.c_void_p(a.data_ptr()), C.c_void_p(s.data_ptr()), C.c_void_p(t.data_ptr()),
                 _ptr(sc), _ptr(out), _stream(self.lib, x0.device)), "ddif_plan_q_sample_forward")

@@ -206,7 +206,7 @@ class DPM_Solver:
             return None
         from ..models.sr3_dwt import UNetSR3
 
-        if not isinstance(meta["model"], UNetSR3) or meta["model_type"] != "x_start" or meta["model_kwargs"]:
+        if not isinstance(meta["model"], UNetSR3) or meta["model_type"] not in ("x_start", "noise", "v") or meta["model_kwargs"]:
             return None
         if meta["guidance_type"] != "classifier-free" or meta["condition"] is None:
             return None
@@ -251,6 +251,7 @@ class DPM_Solver:
             model, cond, clamp = fused
             B, _, H, W = x.shape
             plan = model.plan_for(B, H, W, x.device)
+            plan.set_objective(self._model_fn.ddif["model_type"], plan.objective[1])  # the model_type branch of model_wrapper (reference :296-303) runs in dpm_x0_kernel
             plan.set_cond(cond)
             tabs = dict(n_evals=steps, order=order,
                         t_model=[float((ts[k] - 1.0 / ns.total_N) * 1000.0) for k in range(steps)],

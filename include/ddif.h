@@ -158,6 +158,55 @@ DDIF_API int ddif_plan_q_sample_forward(ddif_plan_t plan, const float* x0, const
                                const float* sqrt_1mac_host, const float* time_host, const float* self_cond,
                                float* pred, void* stream);
 
+/* ---- objective: what the network predicts and which loss trains it ------------------------------------------------------ */
+
+/* GaussianDiffusion(pred_mode=..., loss_type=...) (diffusion/diffusion_ddpm_pan.py:105-107,152-162).  Sticky per plan; a new plan has the engine's
+ * configuration (DDIF_PRED_X_START, DDIF_LOSS_L1), under which every entry point above behaves exactly as before.  With another pred_mode the samplers
+ * and the p_losses entry points treat the network output as the noise / v prediction:
+ *   noise:  x0 = sqrt_recip_alphas_cumprod[t] * x_t - sqrt_recipm1_alphas_cumprod[t] * out      (:298-302 predict_start_from_noise)
+ *   pred_v: x0 = sqrt_alphas_cumprod[t] * x_t - sqrt_one_minus_alphas_cumprod[t] * out          (:310-314 predict_start_from_v)
+ * in front of the clamp (:366-375); ddif_plan_sample_dpmpp takes the matching model_type branch of model_wrapper (solver/dpm_solver.py:296-303:
+ * "noise" eps = out, "v" eps = alpha * out + sigma * x) and needs no further tables.  DDPM / DDIM then need the two coefficient tables of the
+ * conversion (the _ex entry points below); the plain entry points fail with DDIF_ERR_INVALID.  ddif_plan_num_launches does not change. */
+#define DDIF_PRED_X_START 0
+#define DDIF_PRED_NOISE 1
+#define DDIF_PRED_V 2
+#define DDIF_LOSS_L1 0   /* nn.L1Loss  (:152-153) */
+#define DDIF_LOSS_L2 1   /* nn.MSELoss (:154-155) */
+DDIF_API int ddif_plan_set_objective(ddif_plan_t plan, int pred_mode, int loss_type);
+DDIF_API int ddif_plan_get_objective(ddif_plan_t plan, int* pred_mode, int* loss_type);
+
+/* The per-step coefficients of x0 = coef_xt * x_t - coef_out * out (HOST arrays of n_steps floats in execution order, gathered from the schedule
+ * buffers like the other tables): (sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod) for noise, (sqrt_alphas_cumprod,
+ * sqrt_one_minus_alphas_cumprod) for pred_v (:298-314).  NULL / ignored under DDIF_PRED_X_START. */
+typedef struct ddif_pred_tables {
+    int32_t n_steps;
+    const float* coef_xt;
+    const float* coef_out;
+} ddif_pred_tables;
+/* p_sample_loop (:445-507) / ddim_sample_loop (:624-666) with p_mean_variance's pred_mode branch (:366-375).  In the DDIM loop eps is still
+ * recomputed from the unclamped x0 (:605-606). */
+DDIF_API int ddif_plan_sample_ddpm_ex(ddif_plan_t plan, const ddif_ddpm_tables* tabs, const ddif_pred_tables* pred, const float* x_T, const float* noise,
+                                      uint64_t seed, uint64_t tile0, float clamp_lo, float clamp_hi, int do_clamp, float* out, void* stream);
+DDIF_API int ddif_plan_sample_ddim_ex(ddif_plan_t plan, const ddif_ddim_tables* tabs, const ddif_pred_tables* pred, const float* x_T, const float* noise,
+                                      uint64_t seed, uint64_t tile0, float clamp_lo, float clamp_hi, int do_clamp, float* out, void* stream);
+
+/* Per-sample rows of p_losses beyond sqrt_ac / sqrt_1mac (B floats each, HOST or DEVICE like those):
+ *   recon_xt, recon_out: x0 = recon_xt[b] * x_t - recon_out[b] * prediction (:708-713, :724, :735), the schedule pair of ddif_pred_tables gathered at t;
+ *     required unless the plan predicts x_start;
+ *   p2_weight: p2_loss_weight[t_b] (:762-764).  loss_func has already reduced to a scalar there, so the weighting is loss * mean_b(p2_weight[t_b]):
+ *     one factor on the loss and on its gradient.  NULL = no weighting (p2_loss_weight_gamma = 0). */
+typedef struct ddif_objective_rows {
+    const float* recon_xt;
+    const float* recon_out;
+    const float* p2_weight;
+} ddif_objective_rows;
+/* ddif_plan_q_sample_forward under the plan's objective: `pred` (nullable) = the raw network output, `recon` (nullable) = the x0 rebuilt from it -- what
+ * the self-conditioning pass feeds back (:702-714). */
+DDIF_API int ddif_plan_q_sample_forward_ex(ddif_plan_t plan, const float* x0, const float* noise, const float* sqrt_ac_host, const float* sqrt_1mac_host,
+                                           const float* time_host, const float* self_cond, const ddif_objective_rows* rows, float* pred, float* recon,
+                                           void* stream);
+
 /* ---- either side of the denoising loop ---------------------------------------------------------------------------- */
 
 /* Cond assembly of the engine, fused with the level-1 Haar analysis the reference does with PyWavelets on the CPU at
@@ -221,6 +270,13 @@ DDIF_API int ddif_plan_train_forward_backward(ddif_plan_t plan, const float* x, 
                                               float* loss_dev, float* pred, void* stream);
 DDIF_API int ddif_plan_train_step(ddif_plan_t plan, const float* x0, const float* noise, const float* sqrt_ac_host, const float* sqrt_1mac_host,
                                   const float* time_host, const float* self_cond, float* loss_dev, float* pred, void* stream);
+/* ddif_plan_train_step under the plan's objective (ddif_plan_set_objective; :722-766): target x0 / noise / v = a*noise - s*x0 (:304-308) by pred_mode,
+ * F.l1_loss or F.mse_loss (gradient 2 (pred - target) / n) by loss_type, p2 weighting from rows->p2_weight.  pred (nullable): the network output;
+ * recon (nullable): recon_x0 as the reference returns it -- from the prediction for noise (:724), from the TRUE v for pred_v (:734-735: the reference
+ * passes the target there, so its recon_x0 is x_start up to rounding), the prediction itself for x_start. */
+DDIF_API int ddif_plan_train_step_ex(ddif_plan_t plan, const float* x0, const float* noise, const float* sqrt_ac_host, const float* sqrt_1mac_host,
+                                     const float* time_host, const float* self_cond, const ddif_objective_rows* rows, float* loss_dev, float* pred,
+                                     float* recon, void* stream);
 DDIF_API int ddif_plan_train_info(ddif_plan_t plan, int* n_dropout_sites, int* n_droppath_sites);  /* sites in execution order */
 DDIF_API int ddif_plan_train_site(ddif_plan_t plan, int site, int* C, int* H, int* W);             /* mask shape (B, C, H, W) */
 /* explicit masks (parity with a reference run whose masks were captured): mask (B,C,H,W) device; scales HOST [n_droppath][B] */

@@ -6,6 +6,8 @@ written into the repository.
 
     python tools/make_golden.py [--only fwd,sched,ddpm,ddim,dpm,loss,psnr] [--skip-long]
     python tools/make_golden.py --only ddpmbig,dpmbig,ddpmfull     (round 6: the config-exact cases; not part of the default set)
+    python tools/make_golden.py --only objective                   (pred_mode noise / pred_v, l2, p2 weighting: tests/golden_cases_objective.py;
+                                                                    each output also from an fp64 run of the reference; not part of the default set)
 """
 import argparse
 import json
@@ -92,6 +94,191 @@ def make_diffusion(D, net, C, T, size):
                             clamp_range=(0, 1))
     d.set_new_noise_schedule(betas=D.make_beta_schedule(schedule="cosine", n_timestep=T, cosine_s=8e-3))
     return d
+
+
+def make_objective(UNetSR3, D, S, net_for):
+    """The noise / v parameterisations (tests/golden_cases_objective.py).  Every case runs twice: the reference as it is (fp32: the expected output)
+    and the reference in fp64 -- net and diffusion `.double()`, `net.forward` wrapped to cast x / self_cond (the diffusion calls `model.forward`
+    directly, so module hooks on the net do not fire), the positional encoding's output cast -- with the same fp32 random draws.  `<key>_f64` and
+    `gap::<key>` = max|fp32 - fp64| put the case's own noise floor on file."""
+    import copy
+
+    import golden_cases_objective as go
+
+    nets64 = {}
+
+    def net64_for(ds):
+        if ds not in nets64:
+            n = copy.deepcopy(net_for(ds)).double()
+            fwd = n.forward
+            n.forward = lambda x, t, cond=None, self_cond=None: fwd(x.double(), t, None if cond is None else cond.double(), None if self_cond is None else self_cond.double())
+            n.noise_level_mlp[0].register_forward_hook(lambda m, i, o: o.double())
+            nets64[ds] = n
+        return nets64[ds]
+
+    def diffusion(ds, T, size, pred_mode, loss_type="l2", gamma=0.0, f64=False, schedule=None):
+        net = net64_for(ds) if f64 else net_for(ds)
+        d = D.GaussianDiffusion(net, image_size=size, channels=gc.DATASETS[ds][0], pred_mode=pred_mode, loss_type=loss_type, device="cpu", clamp_range=(0, 1),
+                                p2_loss_weight_gamma=gamma)
+        d.set_new_noise_schedule(betas=D.make_beta_schedule(**(schedule or dict(schedule="cosine", n_timestep=T, cosine_s=8e-3))))
+        return d.double() if f64 else d
+
+    too_noisy = []
+
+    def both(run):
+        a, b = run(False), run(True)
+        gap = float((a.double() - b).abs().max())
+        return a, b, gap
+
+    def report(cid, gap, ref, tol):
+        print(f"  {cid}: fp32-fp64 gap {gap:.2e}, max|golden| {ref:.3g}, tolerance {tol:.2e} -> gap / tolerance = {gap / tol:.3f}")
+        if gap > 0.1 * tol:
+            too_noisy.append(cid)
+
+    for stem, ds, B, H, W, T, seed in go.DDPM_CASES:
+        cond = gc.tiles_for(ds, B, H, W, seed=seed)["cond"]
+        for pm in go.PRED_MODES:
+            def run(f64):
+                d = diffusion(ds, T, H, pm, f64=f64)  # (before seeding: building a net draws from the generator)
+                torch.manual_seed(seed)
+                return d(cond.double() if f64 else cond, mode="ddpm_sample")
+            out, out64, gap = both(run)
+            report(f"{stem}_{pm}", gap, float(out.abs().max()), 1e-4)
+            save(f"{stem}_{pm}", out=out, out_f64=out64, gap=gap, cond_chk=chk(cond))
+
+    for stem, ds, B, H, W, T, sect, seed in go.DDIM_CASES:
+        cond = gc.tiles_for(ds, B, H, W, seed=seed)["cond"]
+        for pm in go.PRED_MODES:
+            def run(f64):
+                d = diffusion(ds, T, H, pm, f64=f64)
+                torch.manual_seed(seed)
+                return d(cond.double() if f64 else cond, mode="ddim_sample", section_counts=sect)
+            out, out64, gap = both(run)
+            report(f"{stem}_{pm}", gap, float(out.abs().max()), 1e-4 * max(1.0, float(out.abs().max())))
+            save(f"{stem}_{pm}", out=out, out_f64=out64, gap=gap, cond_chk=chk(cond))
+
+    for stem, ds, H, W, T, steps, order, seed in go.DPM_CASES:
+        C = gc.DATASETS[ds][0]
+        cond = gc.tiles_for(ds, 1, H, W, seed=seed)["cond"]
+        xT = torch.randn(1, C, H, W, generator=torch.Generator().manual_seed(seed))
+        for pm in go.PRED_MODES:
+            def run(f64):
+                d = diffusion(ds, T, H, pm, f64=f64, schedule=go.dpm_schedule(pm, T))
+                cnd, x = (cond.double(), xT.double()) if f64 else (cond, xT)
+                # the schedule scalars (alpha, sigma, lambda, the float model time) stay in the solver's own fp32 in both runs: the twin doubles the
+                # tensor arithmetic -- net and diffusion -- and nothing else
+                ns = S.NoiseScheduleVP("discrete", betas=d.betas.float())
+                lms = cnd[:, :C]
+                fn = S.model_wrapper(d.model, ns, model_type=go.MODEL_TYPE[pm], guidance_type="classifier-free", guidance_scale=1.0, condition=cnd)
+                slv = S.DPM_Solver(fn, ns, algorithm_type="dpmsolver++", correcting_x0_fn=lambda x0, t, lms=lms: (x0 + lms).clamp(0, 1.0) - lms)
+                with torch.no_grad():
+                    return slv.sample(x, steps=steps, order=order, skip_type="time_uniform", method="multistep")
+            out, out64, gap = both(run)
+            report(f"{stem}_{pm}", gap, float(out.abs().max()), 1e-4 * max(1.0, float(out.abs().max())))
+            save(f"{stem}_{pm}", out=out, out_f64=out64, gap=gap, cond_chk=chk(cond))
+
+    def pinned(tt, sc_branch):
+        class Pin:
+            def __enter__(self):
+                self.ri, self.rr = torch.randint, random.random
+                D.torch.randint = lambda *a, **k: tt
+                D.random.random = (lambda: 0.0) if sc_branch else (lambda: 1.0)
+
+            def __exit__(self, *a):
+                D.torch.randint, D.random.random = self.ri, self.rr
+        return Pin()
+
+    for stem, ds, B, H, W, T, tvals, sc_branch, seed in go.LOSS_CASES:
+        C = gc.DATASETS[ds][0]
+        tiles = gc.tiles_for(ds, B, H, W, seed=seed)
+        cond, res = tiles["cond"], tiles["gt"] - tiles["lms"]
+        noise = torch.randn(B, C, H, W, generator=torch.Generator().manual_seed(seed))
+        tt = torch.tensor(tvals, dtype=torch.long)
+        for pm in go.PRED_MODES:
+            arrs = {}
+            for lt in go.LOSS_TYPES:
+                for gamma in go.P2_GAMMAS:
+                    res32 = {}
+
+                    def run(f64, what):
+                        if (f64, "done") not in res32:
+                            d = diffusion(ds, T, H, pm, loss_type=lt, gamma=gamma, f64=f64)
+                            with pinned(tt, sc_branch), torch.no_grad():
+                                cast = (lambda v: v.double()) if f64 else (lambda v: v)
+                                loss, recon = d(cast(res), mode="train", noise=cast(noise), cond=cast(cond))
+                            res32[(f64, "loss")], res32[(f64, "recon")], res32[(f64, "done")] = loss.reshape(1), recon, True
+                        return res32[(f64, what)]
+                    k = go.loss_key(lt, gamma)
+                    loss, loss64, gl = both(lambda f64: run(f64, "loss"))
+                    recon, recon64, gr = both(lambda f64: run(f64, "recon"))
+                    report(f"{stem}_{pm} {k} loss", gl, float(loss), 1e-6)
+                    report(f"{stem}_{pm} {k} recon", gr, float(recon.abs().max()), 2e-5)
+                    arrs.update({f"loss_{k}": loss, f"loss_{k}_f64": loss64, f"gap::loss_{k}": gl, f"recon_{k}": recon, f"recon_{k}_f64": recon64, f"gap::recon_{k}": gr})
+            save(f"{stem}_{pm}", cond_chk=chk(cond), **arrs)
+
+    for cid, ds, B, H, W, T, tvals, pm, lt, gamma, seed in go.GRAD_CASES:
+        C = gc.DATASETS[ds][0]
+        tiles = gc.tiles_for(ds, B, H, W, seed=seed)
+        cond, res = tiles["cond"], tiles["gt"] - tiles["lms"]
+        noise = torch.randn(B, C, H, W, generator=torch.Generator().manual_seed(seed))
+        tt = torch.tensor(tvals, dtype=torch.long)
+        drops, paths = [], []
+
+        def run(f64):
+            d = diffusion(ds, T, H, pm, loss_type=lt, gamma=gamma, f64=f64)
+            net = d.model
+            hooks, k = [], [0, 0]
+            for m in net.modules():  # fp32 run: capture the masks (execution order); fp64 run: impose them
+                if isinstance(m, nn.Dropout):
+                    if not f64:
+                        hooks.append(m.register_forward_hook(lambda mod, inp, out: drops.append(((out != 0) | (inp[0] == 0)).detach())))
+                    else:
+                        def imp(mod, inp, out):
+                            k[0] += 1
+                            return inp[0] * drops[k[0] - 1].double() / (1 - mod.p)
+                        hooks.append(m.register_forward_hook(imp))
+                elif type(m).__name__ == "DropPath":
+                    if not f64:
+                        hooks.append(m.register_forward_hook(lambda mod, inp, out: paths.append(((out.detach().flatten(1).abs().sum(1) != 0).float() / (1 - mod.drop_prob)))))
+                    else:
+                        def impp(mod, inp, out):
+                            k[1] += 1
+                            return inp[0] * paths[k[1] - 1].double().reshape(-1, 1, 1, 1)
+                        hooks.append(m.register_forward_hook(impp))
+            net.train()
+            for prm in net.parameters():
+                prm.requires_grad_(True)
+                prm.grad = None
+            torch.manual_seed(seed)
+            cast = (lambda v: v.double()) if f64 else (lambda v: v)
+            try:
+                with pinned(tt, False):
+                    loss, recon = d(cast(res), mode="train", noise=cast(noise), cond=cast(cond))
+                loss.backward()
+            finally:
+                net.eval()
+                for hk in hooks:
+                    hk.remove()
+            names = [n for n, _ in net.named_parameters()]
+            norms = np.array([float(prm.grad.double().norm()) if prm.grad is not None else -1.0 for _, prm in net.named_parameters()], dtype=np.float64)
+            full = {"grad::" + n: prm.grad.detach().clone() for n, prm in net.named_parameters() if any(n == f or n.startswith(f) for f in go.TRAIN_GRAD_FULL)}
+            for prm in net.parameters():
+                prm.grad = None
+                prm.requires_grad_(False)
+            return float(loss.detach()), recon.detach(), names, norms, full
+
+        loss, recon, names, norms, full = run(False)
+        loss64, recon64, _, norms64, full64 = run(True)
+        rel = float(np.max(np.abs(norms - norms64) / np.maximum(norms64, 1e-4)))
+        gfull = max(float((full[k].double() - full64[k]).abs().max()) / max(float(full64[k].abs().max()), 1e-5) for k in full)
+        print(f"  {cid}: loss gap {abs(loss - loss64):.2e} (tolerance 1e-6), worst relative grad-norm gap {rel:.2e} (tolerance 2e-4), worst relative full-gradient gap {gfull:.2e} (tolerance 5e-5)")
+        if not (abs(loss - loss64) <= 1e-7 and rel <= 2e-5 and gfull <= 5e-6):
+            too_noisy.append(cid)
+        arrs = {f"drop_{k}": np.packbits(d_.numpy().reshape(-1)) for k, d_ in enumerate(drops)}
+        arrs.update({f"drop_{k}_shape": np.array(d_.shape) for k, d_ in enumerate(drops)})
+        save(cid, loss=loss, loss_f64=loss64, recon=recon, recon_f64=recon64, n_drop=len(drops), paths=torch.stack(paths), p_drop=0.2, names=np.array(names), grad_norms=norms,
+             grad_norms_f64=norms64, **{"gap::loss": abs(loss - loss64), "gap::grad_norms_rel": rel, "gap::grad_full_rel": gfull}, **arrs, **full)
+    assert not too_noisy, f"the reference's own fp32-fp64 gap exceeds a tenth of the tolerance: change these cases: {too_noisy}"
 
 
 def main():
@@ -345,6 +532,9 @@ def main():
             finally:
                 D.torch.randint, D.random.random = _ri, _rr
             save(cid, loss=loss, recon=recon, cond_chk=chk(cond))
+
+    if "objective" in only:
+        make_objective(UNetSR3, D, S, net_for)
 
     if "psnr" in only:
         import importlib.util
