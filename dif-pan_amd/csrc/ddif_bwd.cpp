@@ -8,8 +8,8 @@
 namespace ddif {
 // DDIF_TRAIN_X3=0: the training convs (forward and dgrad) on the exact-fp32 MFMA instead of the bf16x3 split products the inference path uses
 // (same fp32-class accuracy, ~2.5x the matrix rate; kernels_conv.h MATH = 1).  The weight gradient always runs on the exact instruction.
-static bool train_x3() {
-    static const bool v = [] { const char* e = getenv("DDIF_TRAIN_X3"); return !e || atoi(e) != 0; }();
+bool train_x3() {
+    static const bool v = env_flag("DDIF_TRAIN_X3", true);
     return v;
 }
 static inline dim3 grid_for(size_t n) {
@@ -411,7 +411,7 @@ WgradGeom wgrad_geom(int B, int Cin, int Cout, int H, int W, bool centre) {  // 
     g.n_ci = (Cin + 31) / 32;
     // rows per band: the largest of {16, 8, 4, 2, 1} (<= H) whose two tiles fit DDIF_WGRAD_SMEM_KB (default 72 KB: two workgroups per CU, so one's
     // band loads overlap the other's MFMAs; the low-resolution levels then stage a whole 8x8 sample or half a 16x16 one per band)
-    static const size_t lim = [] { const char* e = getenv("DDIF_WGRAD_SMEM_KB"); return (size_t)(e ? atoi(e) : 72) * 1024; }();
+    static const size_t lim = (size_t)env_int("DDIF_WGRAD_SMEM_KB", 72) * 1024;
     g.pf = 0;
     g.centre = centre ? 1 : 0;
     const int halo = centre ? 0 : 1;
@@ -448,7 +448,7 @@ WgradGeom wgrad_geom(int B, int Cin, int Cout, int H, int W, bool centre) {  // 
     if (g.rb < 1) g.rb = 0;  // W too wide (caller checks)
     // the bf16x3 kernel (kernels_bwd.h conv3x3_wgrad_x3_kernel; DDIF_WGRAD_X3=0: the fp32 kernel everywhere): 8 | W, W <= 128; the largest band of <= 256 staging
     // items (RB rows of dY + RB new rows of X) whose transposed bf16 tiles fit two workgroups per CU (failing that, one)
-    static const bool x3_env = [] { const char* e = getenv("DDIF_WGRAD_X3"); return !e || atoi(e) != 0; }();
+    static const bool x3_env = env_flag("DDIF_WGRAD_X3", true);
     if (x3_env && W % 8 == 0 && W <= 128) {
         auto stride = [](int n) { return n + (((n / 8) % 2 == 0) ? 8 : 0); };  // an odd number of 16-byte slots
         const int segs = W / 8, hl = centre ? 0 : 1, xw = centre ? W : W + 16;

@@ -37,7 +37,7 @@ int la_launch_t(const LaFuseArgs& a, int nbq, int nba, int grid, hipStream_t s, 
 
 // shapes the fused kernel carries: whole columns of 64 or 32 rows, 64 / 96 / 128 feature channels, 32 / 64 output channels
 bool lafuse_supported(int H, int fea, int dout) {
-    static const bool la6 = [] { const char* e = getenv("DDIF_LA6"); return !e || atoi(e) != 0; }();  // DDIF_LA6=0: the 192-channel block of the 16 x 16 level as three launches (rounds 4-5)
+    static const bool la6 = env_flag("DDIF_LA6", true);  // DDIF_LA6=0: the 192-channel block of the 16 x 16 level as three launches (rounds 4-5)
     if (H == 16 && fea == 192 && dout == 64 && la6) return true;
     return (H == 64 || H == 32 || H == 16) && fea % 32 == 0 && fea >= 64 && fea <= 128 && dout % 32 == 0 && dout >= 32 && dout <= 64;
 }

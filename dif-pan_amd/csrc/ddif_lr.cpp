@@ -64,13 +64,16 @@ size_t attn_block_smem() { return AttnBlockGeom::smem; }
 // (profiles/r06/attn_block_stamps.txt): 22.3 vs 23.3 us per launch -- the block is bound by the matrix pipe of its ONE CU (qkv: 288 bf16 MFMAs per wave = 9.2 k of the
 // 12.8 k cycles of that stage; attention core on the exact fp32 MFMA: 8.2 k of 22.4 k), a second wave per SIMD has no idle pipe to fill.  Four stays the default.
 static int attn_nw() {
-    static const int v = [] { const char* e = getenv("DDIF_ATTN_NW"); return (e && atoi(e) == 8) ? 8 : 4; }();
+    static const int v = env_int("DDIF_ATTN_NW", 4) == 8 ? 8 : 4;
     return v;
 }
 // DDIF_ATTN_SPLIT = 1 / 2: one / two workgroups per sample instead of four (round 6, kernels_attn.h SPLIT: the query tokens of a sample on up to four CUs, k and v
 // recomputed by each, no exchange); same values.  Measured at B = 64: 22.5 / 16.6 / 15.8 us per launch, 3.418 / 3.366 / 3.344 ms per step (profiles/r06/attn_split_ab.txt)
 int attn_block_split() {
-    static const int v = [] { const char* e = getenv("DDIF_ATTN_SPLIT"); const int x = e ? atoi(e) : 4; return (x == 1 || x == 2) ? x : 4; }();
+    static const int v = [] {
+        const int x = env_int("DDIF_ATTN_SPLIT", 4);
+        return (x == 1 || x == 2) ? x : 4;
+    }();
     return attn_nw() == 8 ? 1 : v;
 }
 int attn_block_prepare() {

@@ -28,52 +28,51 @@ ConvVariant get_conv_variant(int ks, int stride, int ups, int ck, int pro, int c
 }
 
 static int num_cus();
-static int x3_enabled() {  // DDIF_X3=0: the exact-fp32 MFMA instantiation everywhere (bitwise an fmaf chain); covered by tests/test_env_switches.py
-    static const int x3 = [] { const char* e = getenv("DDIF_X3"); return e ? atoi(e) : 1; }();
-    return x3;
-}
-static int f16_enabled() {  // DDIF_F16=0: the split-operand convs stay on bf16x3 (six products) instead of f16x2 (three); tests/test_env_switches.py
-    static const int f16 = [] { const char* e = getenv("DDIF_F16"); return e ? atoi(e) : 1; }();
-    return f16;
-}
+// DDIF_X3=0: the exact-fp32 MFMA instantiation everywhere (bitwise an fmaf chain); covered by tests/test_env_switches.py
+static int x3_enabled() { static const int v = env_int("DDIF_X3", 1); return v; }
+// DDIF_F16=0: the split-operand convs stay on bf16x3 (six products) instead of f16x2 (three); tests/test_env_switches.py
+static int f16_enabled() { static const int v = env_int("DDIF_F16", 1); return v; }
 int g_math_mode = [] { const char* e = getenv("DDIF_MATH"); return (e && std::strcmp(e, "bf16") == 0) ? 1 : 0; }();
-int g_f16_raw = [] { const char* e = getenv("DDIF_F16_RAW"); return e ? (atoi(e) != 0) : 1; }();
-static int lr_rows_enabled() {  // DDIF_LR_ROWS=0: the low-resolution 3x3 convs keep the general (pixel-item) staging where the row staging applies
-    static const int v = [] { const char* e = getenv("DDIF_LR_ROWS"); return e ? atoi(e) : 1; }();
-    return v;
-}
-static int lafuse_enabled() {  // DDIF_LAFUSE=0: the decoder's linear-attention half as three launches (q conv, column statistics, attn_out conv)
-    static const int v = [] { const char* e = getenv("DDIF_LAFUSE"); return e ? atoi(e) : 1; }();
-    return v;
-}
+int g_f16_raw = env_flag("DDIF_F16_RAW", true);
+// DDIF_LR_ROWS=0: the low-resolution 3x3 convs keep the general (pixel-item) staging where the row staging applies
+static int lr_rows_enabled() { static const int v = env_int("DDIF_LR_ROWS", 1); return v; }
+// DDIF_LAFUSE=0: the decoder's linear-attention half as three launches (q conv, column statistics, attn_out conv)
+static int lafuse_enabled() { static const int v = env_int("DDIF_LAFUSE", 1); return v; }
 // DDIF_XCD (bit mask, default 15 = all): XCD-contiguous work partition (ddif_dev.h wg_work_range) of 1 = the general conv kernel, 2 = the low-resolution kernel,
 // 4 = the fused linear-attention block, 8 = the per-sample kernels (bottleneck attention block, gn_dw3x3 of the low levels).  The dispatcher puts workgroup b on
 // XCD b % 8; with the map every kernel of the step gives XCD k the same eighth of the samples (tiles 8 k .. 8 k + 7 at B = 64), so halos, the cout tiles of a pixel
 // tile and a consumer's input (written by the same XCD one launch earlier) meet in that XCD's private L2: 3.90 -> 3.76 ms per denoising step, same box
 // (profiles/r05/k_xcd_ab.txt).  Results do not depend on it -- the partition only decides WHICH workgroup computes an item (tests/test_env_switches.py).
-static int xcd_mask() {
-    static const int v = [] { const char* e = getenv("DDIF_XCD"); return e ? atoi(e) : 15; }();
-    return v;
+static int xcd_mask() { static const int v = env_int("DDIF_XCD", 15); return v; }
+// DDIF_LA8=0: the decoder's linear-attention half at the 8 x 8 level as three launches (rounds 3-5) instead of the fused kernel of round 6 (kernels_lafuse8.h)
+static int la8_enabled() { static const int v = env_int("DDIF_LA8", 1); return v; }
+// DDIF_XF=0: CondInjection.x_conv + FiLM as a launch of its own everywhere (the form of rounds 1-5); tests/test_env_switches.py
+static int xf_enabled() { static const int v = env_int("DDIF_XF", 1); return v; }
+// DDIF_LR=0: the 8x8 / 16x16 levels on the general conv kernel (kernels_conv.h) as well; covered by tests/test_env_switches.py
+static int lr_enabled() { static const int v = env_int("DDIF_LR", 1); return v; }
+// 16 x 16-pixel tiles on eight waves where they fill the CUs; below that (8-16 tiles per GPU: what one rank of a strong-scaling run holds) the four-wave
+// 8 x 16 tiling gives twice the workgroups and every wave a SIMD to itself.  Results do not depend on the choice bit for bit: same products per pixel, and
+// the 16 x 16 tilings write their statistics partials per 8 x 16 half tile (ConvArgs::st_halves).  DDIF_TILE16=1 / 0 forces one form.
+static bool tile16_fills(long items16) {
+    static const int tile16_env = env_int("DDIF_TILE16", -1);
+    return tile16_env >= 0 ? tile16_env != 0 : items16 >= num_cus();
 }
-static int la8_enabled() {  // DDIF_LA8=0: the decoder's linear-attention half at the 8 x 8 level as three launches (rounds 3-5) instead of the fused kernel of round 6 (kernels_lafuse8.h)
-    static const int v = [] { const char* e = getenv("DDIF_LA8"); return e ? atoi(e) : 1; }();
-    return v;
-}
-static int xf_enabled() {  // DDIF_XF=0: CondInjection.x_conv + FiLM as a launch of its own everywhere (the form of rounds 1-5); tests/test_env_switches.py
-    static const int v = [] { const char* e = getenv("DDIF_XF"); return e ? atoi(e) : 1; }();
-    return v;
-}
-static int lr_enabled() {  // DDIF_LR=0: the 8x8 / 16x16 levels on the general conv kernel (kernels_conv.h) as well; covered by tests/test_env_switches.py
-    static const int lr = [] { const char* e = getenv("DDIF_LR"); return e ? atoi(e) : 1; }();
-    return lr;
-}
+// what pick_cfg() decides from: the conv's shape and which arithmetic / kernel families it may take
+struct CfgQuery {
+    int ks, ck, pro, vec, stride, ups, Hout, Wout, Cout, B, cin, c0;
+    bool allow_lr = true;  // the low-resolution kernel may be chosen
+    bool exact = false;    // exact-fp32 MFMA asked for (ConvSpec::exact)
+    bool f16ok = false;    // f16x2 is admissible for this conv
+    bool b1 = false;       // bf16x1 (the throughput variant)
+};
 // cfg 20 / 21: the low-resolution kernel (kernels_lr.h) with 8x8 / 8x16 pixel tiles -- samples of <= 256 pixels whose
 // channel counts fit its 16-channel slabs
-static int pick_cfg(int ks, int ck, int pro, int vec, int stride, int ups_, int Hout, int Wout, int Cout, int B, int cin, int c0, bool allow_lr = true, bool exact = false, bool f16ok = false, bool b1 = false) {
+static int pick_cfg(const CfgQuery& q) {
+    const int ks = q.ks, ck = q.ck, pro = q.pro, vec = q.vec, stride = q.stride, ups_ = q.ups, Hout = q.Hout, Wout = q.Wout, Cout = q.Cout, B = q.B;
+    const bool f16ok = q.f16ok, b1 = q.b1;
     const bool wide = (Wout >= 16) && stride == 1;
-    (void)pro;
-    const bool x3 = x3_enabled() && !exact;
-    if (allow_lr && x3 && lr_enabled() && vec == 1 && stride == 1 && !ups_ && Hout * Wout <= 256 && Cout % 4 == 0 && cin % 16 == 0 && c0 % 16 == 0 &&
+    const bool x3 = x3_enabled() && !q.exact;
+    if (q.allow_lr && x3 && lr_enabled() && vec == 1 && stride == 1 && !ups_ && Hout * Wout <= 256 && Cout % 4 == 0 && q.cin % 16 == 0 && q.c0 % 16 == 0 &&
         ck == (ks == 3 ? 16 : 32))
         // (smaller tiles -- 4 x 8 pixels at the 8 x 8 level, 8 x 8 at 16 x 16: twice the workgroups, each with half the matrix work -- measured
         //  SLOWER, 1.375 -> 1.42 / 1.49 / 1.54 ms for the class, profiles/r04/f_lr_tiles_ab.txt: the items are latency chains that also stream the
@@ -89,23 +88,16 @@ static int pick_cfg(int ks, int ck, int pro, int vec, int stride, int ups_, int 
     }
     if (ks == 3 && vec == 1 && stride == 1 && x3) {
         const bool f16 = f16ok && (pro == PRO_NONE || pro == PRO_GN_SILU);
-        // 16 x 16-pixel tiles on eight waves where they fill the CUs; below that (8-16 tiles per GPU: what one rank of a strong-scaling run holds) the four-wave
-        // 8 x 16 tiling gives twice the workgroups and every wave a SIMD to itself.  Results do not depend on the choice bit for bit: same products per pixel, and
-        // the 16 x 16 tilings write their statistics partials per 8 x 16 half tile (ConvArgs::st_halves).  DDIF_TILE16=1 / 0 forces one form.
-        static const int tile16_env = [] { const char* e = getenv("DDIF_TILE16"); return e ? atoi(e) : -1; }();
         const long items16 = (long)B * ((Hout + 15) / 16) * ((Wout + 15) / 16) * ((Cout + 31) / 32);
-        const bool big = tile16_env >= 0 ? tile16_env != 0 : items16 >= num_cus();
-        if (wide && Hout >= 32 && Wout >= 32 && big) return b1 ? 47 : (f16 ? 27 : 7);
+        if (wide && Hout >= 32 && Wout >= 32 && tile16_fills(items16)) return b1 ? 47 : (f16 ? 27 : 7);
         if (wide || Cout <= 32) return b1 ? 48 : (f16 ? 28 : 8);
         return b1 ? 49 : (f16 ? 29 : 9);
     }
-    static const bool s2_f16 = [] { const char* e = getenv("DDIF_S2_F16"); return !e || atoi(e) != 0; }();  // DDIF_S2_F16=0: the Downsample convs and the stem stay on the exact-fp32 tilings
+    static const bool s2_f16 = env_flag("DDIF_S2_F16", true);  // DDIF_S2_F16=0: the Downsample convs and the stem stay on the exact-fp32 tilings
     if (ks == 3 && vec == 1 && stride == 2 && !ups_ && x3 && f16ok && !b1 && s2_f16 && pro == PRO_NONE && Wout >= 16) return Cout <= 32 ? 28 : 29;
     if (ks == 3 && vec == 2 && stride == 1 && !ups_ && x3 && f16ok && !b1 && s2_f16 && pro == PRO_NONE && wide && Cout <= 32) {  // the stem
-        static const int tile16_env = [] { const char* e = getenv("DDIF_TILE16"); return e ? atoi(e) : -1; }();
         const long items16 = (long)B * ((Hout + 15) / 16) * ((Wout + 15) / 16);
-        const bool big = tile16_env >= 0 ? tile16_env != 0 : items16 >= num_cus();
-        return (Hout >= 32 && Wout >= 32 && big) ? 27 : 28;
+        return (Hout >= 32 && Wout >= 32 && tile16_fills(items16)) ? 27 : 28;
     }
     if (ks == 3 && vec == 1 && wide && !ups_) {
         const long items32 = (long)B * ((Hout + 15) / 16) * ((Wout + 15) / 16) * ((Cout + 31) / 32);
@@ -151,14 +143,11 @@ static inline void launch_dw3x3(hipStream_t s, const DwArgs& a) {
     else hipLaunchKernelGGL(dw3x3_kernel, grid, dim3(256), 10 * 18 * 32 * sizeof(float), s, a);
 }
 
-
 // ------------------------------------------------------------------------------------------------ allocation
 Plan::~Plan() {
     drop_graphs();
 #ifndef DDIF_EMU
     if (cap_stream) (void)hipStreamDestroy(cap_stream);
-#endif
-#ifndef DDIF_EMU
     if (wg_stream) {
         (void)hipStreamSynchronize(wg_stream);
         (void)hipStreamDestroy(wg_stream);
@@ -309,6 +298,13 @@ int Plan::build() {
     return 0;
 }
 
+// a conv kernel whose LDS need (variant + the launch's staging extra) passes 64 KiB: the attribute is per kernel function, set to the variant's maximum
+static int raise_dynamic_lds(ConvKernelFn fn, size_t var_smem) {
+    if (var_smem + 8192 > 64 * 1024)
+        DDIF_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(var_smem + 8192)));
+    return 0;
+}
+
 int Plan::add_conv(std::vector<Op>& prog, const ConvSpec& s, Tensor* out) {
     const PackedConv& pc = *s.pc;
     const int Hin = s.in0.H, Win = s.in0.W;
@@ -334,29 +330,39 @@ int Plan::add_conv(std::vector<Op>& prog, const ConvSpec& s, Tensor* out) {
     const bool b1ok = math_mode == 1 && !train_mode && pc.w_b1 && !s.w_override && !s.exact;
     const bool f16ok0 = f16ok;
     if (b1ok) f16ok = false;
-    int math = b1ok ? MATH_BF16X1 : (f16ok ? MATH_F16X2 : MATH_BF16X3);
-    int cfg = pick_cfg(pc.ks, pc.ck, s.pro, vec, s.stride, s.ups, Hout, Wout, pc.cout, B, c0 + c1, c1 ? c0 : c0 + c1, true, s.exact, f16ok, b1ok);
     const int epi = (s.film ? EPI_FILM : 0) | (s.res ? EPI_RES : 0) | (pc.cout % 4 != 0 ? EPI_SOUT : 0) | (s.silu ? EPI_SILU : 0) | (s.cso_mx ? EPI_COLST : 0);
+    // one way to ask: choose(...) picks cfg (and the operand format that goes with it) for this conv's shape, variant(cfg, epi) looks the instantiation up
+    CfgQuery q{pc.ks, pc.ck, s.pro, vec, s.stride, s.ups, Hout, Wout, pc.cout, B, c0 + c1, c1 ? c0 : c0 + c1};
+    q.exact = s.exact;
+    int cfg = 0, math = MATH_BF16X3;
+    auto choose = [&](bool allow_lr, bool f16, bool b1) {
+        q.allow_lr = allow_lr;
+        q.f16ok = f16;
+        q.b1 = b1;
+        math = b1 ? MATH_BF16X1 : (f16 ? MATH_F16X2 : MATH_BF16X3);
+        cfg = pick_cfg(q);
+    };
+    auto variant = [&](int cfg_, int epi_) { return get_conv_variant(pc.ks, s.stride, s.ups, pc.ck, s.pro, cfg_, vec, epi_, math); };
+    choose(true, f16ok, b1ok);
     if (s.cso_mx && ((cfg != 20 && cfg != 21) || Hout > (cfg == 20 ? 8 : 16)))
         return fail(DDIF_ERR_INVALID, "%s: column statistics epilogue needs the low-resolution kernel and H <= 16", s.name);
-    static const bool wres_env = [] { const char* e = getenv("DDIF_WRES"); return !e || atoi(e) != 0; }();  // DDIF_WRES=0: tiling 27 everywhere (tests/test_env_switches.py)
-    if (cfg == 27 && wres_env && c0 == 32 && c1 == 0 && pc.cout <= 32 && pc.ck == 16 && pc.n_chunks == 2 && !s.w_override && s.w_bstride == 0 &&
-        get_conv_variant(pc.ks, s.stride, s.ups, pc.ck, s.pro, 37, vec, epi, math).fn)
+    static const bool wres_env = env_flag("DDIF_WRES", true);  // DDIF_WRES=0: tiling 27 everywhere (tests/test_env_switches.py)
+    if (cfg == 27 && wres_env && c0 == 32 && c1 == 0 && pc.cout <= 32 && pc.ck == 16 && pc.n_chunks == 2 && !s.w_override && s.w_bstride == 0 && variant(37, epi).fn)
         cfg = 37;
-    ConvVariant var = get_conv_variant(pc.ks, s.stride, s.ups, pc.ck, s.pro, cfg, vec, epi, math);
-    if (!var.fn && (cfg == 20 || cfg == 21)) {  // prologue / epilogue combination the low-resolution kernel does not carry
-        cfg = pick_cfg(pc.ks, pc.ck, s.pro, vec, s.stride, s.ups, Hout, Wout, pc.cout, B, c0 + c1, c1 ? c0 : c0 + c1, false, false, f16ok, b1ok);
-        var = get_conv_variant(pc.ks, s.stride, s.ups, pc.ck, s.pro, cfg, vec, epi);
-    }
-    if (!var.fn && b1ok) {  // a combination the throughput variant does not instantiate: the default path of this conv
+    ConvVariant var = variant(cfg, epi);
+    // the fallback ladder: low-resolution kernel -> general kernel (a prologue / epilogue combination the low-resolution kernel does not carry), and
+    // bf16x1 -> the default math of this conv (a combination the throughput variant does not instantiate)
+    auto general_kernel_if_no_lr = [&](bool f16, bool b1) {
+        if (var.fn || (cfg != 20 && cfg != 21)) return;
+        choose(false, f16, b1);
+        var = variant(cfg, epi);
+    };
+    general_kernel_if_no_lr(f16ok, b1ok);
+    if (!var.fn && b1ok) {
         f16ok = f16ok0;
-        math = f16ok ? MATH_F16X2 : MATH_BF16X3;
-        cfg = pick_cfg(pc.ks, pc.ck, s.pro, vec, s.stride, s.ups, Hout, Wout, pc.cout, B, c0 + c1, c1 ? c0 : c0 + c1, true, s.exact, f16ok, false);
-        var = get_conv_variant(pc.ks, s.stride, s.ups, pc.ck, s.pro, cfg, vec, epi, math);
-        if (!var.fn && (cfg == 20 || cfg == 21)) {
-            cfg = pick_cfg(pc.ks, pc.ck, s.pro, vec, s.stride, s.ups, Hout, Wout, pc.cout, B, c0 + c1, c1 ? c0 : c0 + c1, false, false, f16ok, false);
-            var = get_conv_variant(pc.ks, s.stride, s.ups, pc.ck, s.pro, cfg, vec, epi);
-        }
+        choose(true, f16ok, false);
+        var = variant(cfg, epi);
+        general_kernel_if_no_lr(f16ok, false);
     }
     if (!var.fn) return fail(DDIF_ERR_INVALID, "%s: no kernel variant (ks=%d stride=%d ups=%d ck=%d pro=%d cfg=%d vec=%d epi=%d)", s.name, pc.ks, s.stride, s.ups, pc.ck, s.pro, cfg, vec, epi);
     // round 6: a low-resolution 3x3 conv whose tile spans the whole image width (the 8x8 / 16x16 levels of a 64x64 tile) stages by rows (kernels_lr.h ROWS): same
@@ -472,39 +478,34 @@ int Plan::add_conv(std::vector<Op>& prog, const ConvSpec& s, Tensor* out) {
     if (g_debug_grid_cap > 0 && g_debug_grid_cap < cap) cap = g_debug_grid_cap;
     const dim3 grid((unsigned)(nwork < cap ? nwork : cap), 1u);
     const dim3 block((unsigned)var.nthr);
-    if (var.smem + 8192 > 64 * 1024) {  // the attribute is per kernel function: set it to the variant's maximum
-        DDIF_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(var.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(var.smem + 8192)));
-    }
+    if (int e = raise_dynamic_lds(var.fn, var.smem)) return e;
     if (smem > var.smem + 8192) return fail(DDIF_ERR_INVALID, "%s: %d input channels exceed the GroupNorm staging area", s.name, c0 + c1);
     // convs with a time bias: in the samplers every sample shares the step's row (bias + row live in LDS); forward() /
     // q_sample_forward with one t per sample use the EPI_TBS instantiation (rows loaded per work item)
     ConvKernelFn fn_tbs = nullptr;
     if (s.tb_off >= 0) {
-        const ConvVariant vt = get_conv_variant(pc.ks, s.stride, s.ups, pc.ck, s.pro, cfg, vec, epi | EPI_TBS, math);
+        const ConvVariant vt = variant(cfg, epi | EPI_TBS);
         if (!vt.fn || vt.smem != var.smem) return fail(DDIF_ERR_INVALID, "%s: no per-sample time-bias kernel variant", s.name);
         fn_tbs = lr_rows ? var.fn : vt.fn;  // (the low-resolution kernel reads its time-bias rows from memory either way: ddif_lr.cpp)
-        if (var.smem + 8192 > 64 * 1024)
-            DDIF_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn_tbs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(var.smem + 8192)));
+        if (int e = raise_dynamic_lds(fn_tbs, var.smem)) return e;
     }
     // the final conv: the same tiling with the DDPM / DDIM update in its epilogue (split-operand tilings, vector output path)
     ConvKernelFn fn_samp = nullptr;
     if (s.samp && !train_mode && epi == 0 && s.tb_off < 0 && &prog == &step) {
-        const ConvVariant vs = get_conv_variant(pc.ks, s.stride, s.ups, pc.ck, s.pro, cfg, vec, EPI_SAMP, math);
+        const ConvVariant vs = variant(cfg, EPI_SAMP);
         if (vs.fn && vs.smem == var.smem) {
             fn_samp = vs.fn;
-            if (var.smem + 8192 > 64 * 1024)
-                DDIF_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn_samp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(var.smem + 8192)));
+            if (int e = raise_dynamic_lds(fn_samp, var.smem)) return e;
             final_fused = true;
         }
     }
     // ... and with the noise / v prediction turned into x0 in front of the update (EPI_PRED: its own instantiation, ddif_plan_set_objective)
     ConvKernelFn fn_samp_pred = nullptr;
     if (fn_samp) {
-        const ConvVariant vp = get_conv_variant(pc.ks, s.stride, s.ups, pc.ck, s.pro, cfg, vec, EPI_SAMP | EPI_PRED, math);
+        const ConvVariant vp = variant(cfg, EPI_SAMP | EPI_PRED);
         if (vp.fn && vp.smem == var.smem) {
             fn_samp_pred = vp.fn;
-            if (var.smem + 8192 > 64 * 1024)
-                DDIF_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn_samp_pred), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(var.smem + 8192)));
+            if (int e = raise_dynamic_lds(fn_samp_pred, var.smem)) return e;
             final_fused_pred = true;
         }
     }
@@ -574,204 +575,225 @@ int Plan::add_conv(std::vector<Op>& prog, const ConvSpec& s, Tensor* out) {
 }
 
 // ------------------------------------------------------------------------------------------------ program
-int Plan::build_impl() {
-    const ddif_net_cfg& c = net->cfg;
-    if (!net->committed) return fail(DDIF_ERR_STATE, "ddif_plan_create: ddif_net_commit has not been called");
-    C = c.out_channel;
-    P = c.pan_channel;
-    const int Cl = c.lms_channel;
-    CC = 2 * Cl + 4 * P;
-    const int nlev = c.n_channel_mults;
-    const int div = 1 << (nlev - 1);
-    if (B < 1 || H < div || W < div || H % div || W % div)
-        return fail(DDIF_ERR_INVALID, "ddif_plan_create: H=%d W=%d must be positive multiples of %d", H, W, div);
-    LH.assign(1, H);
-    LW.assign(1, W);
-    for (int l = 1; l < nlev; ++l) {
-        LH.push_back((LH.back() - 1) / 2 + 1);
-        LW.push_back((LW.back() - 1) / 2 + 1);
-    }
-    auto V = [&](const std::string& k) -> const float* {
-        auto it = net->vec.find(k);
-        return it == net->vec.end() ? nullptr : it->second;
-    };
-    auto PC = [&](const std::string& k) -> const PackedConv* {
-        auto it = net->conv.find(k);
-        return it == net->conv.end() ? nullptr : &it->second;
-    };
+namespace {
 #define DDIF_TRY(x) do { if (int e__ = (x)) return e__; } while (0)
 
-    // ---- boundary staging + sampler state
-    DDIF_TRY(dalloc(&zeros, (size_t)1024));
-    if (!dry) DDIF_HIPCHK(hipMemset(zeros, 0, 1024 * sizeof(float)));
-    DDIF_TRY(alloc_tensor(&x_in, c.in_channel, H, W));
-    DDIF_TRY(alloc_tensor(&sc_in, c.out_channel, H, W));
-    DDIF_TRY(alloc_tensor(&lms, C, H, W));
-    const size_t img_n = (size_t)B * H * W * C;
-    for (int i = 0; i < 2; ++i) DDIF_TRY(dalloc(&img[i], img_n));
-    for (int i = 0; i < 3; ++i) DDIF_TRY(dalloc(&mbuf[i], img_n));
-    DDIF_TRY(dalloc(&io_nchw, (size_t)B * H * W * (c.in_channel > C ? c.in_channel : C)));
-    DDIF_TRY(dalloc(&small, (size_t)4 * B + 64));
+// One pass of the plan builder: the state UNetSR3.forward threads through its layers (reference models/sr3_dwt.py:169-219) and one method per stage.
+// Plan::build_impl() below is the table of contents.  Every method appends launches to p.step (per denoising step) or p.pre (cond-only, run by set_cond); the
+// ORDER of their alloc_tensor / dalloc / use() / push_back calls is part of the result (arena placement, tests/test_plan_signature.py).
+struct PlanBuilder {
+    Plan& p;
+    const Net& net;
+    const ddif_net_cfg& c;
+    const bool train;
+    const int B, Cl, Pn, nlev;
+    std::vector<Op>&pre, &step;
 
-    // ---- cond-only program (set_cond)
-    cenc.resize(nlev);
-    cdec.resize(nlev);
-    {
-        Op op;
-        op.name = "lms_nhwc";
-        Tensor lm = lms;
-        const int BB = B, CCc = CC, HW = H * W, Cc = C;
-        op.run = [this, lm, BB, CCc, HW, Cc](hipStream_t s, const StepCtx&) {
-            hipLaunchKernelGGL(nchw_to_nhwc_kernel, ew_grid((size_t)BB * HW * Cc), dim3(256), 0, s, (const float*)this->cond_nchw, BB, CCc, HW, 0, Cc, lm.p);
-        };
-        pre.push_back(std::move(op));
+    Tensor cur;                 // the chain tensor
+    std::vector<Tensor> feats;  // skip connections
+    std::vector<int> feat_mod;  // train: index in tmods of the module that produced each feature
+    int lev = 0;
+    // cond-only FiLM branch of an encoder block: body(cond) -> scale | shift (sr3_dwt.py:379-391); built when first asked for -- by the block itself, or one
+    // layer earlier by the conv that folds the block's x_conv + FiLM into its epilogue (round 6)
+    std::map<const Layer*, std::pair<Tensor, Tensor>> film_cache;  // block -> (hid, film)
+    // the fold request a producer conv at index li (stem / Downsample / the last conv of a block) hands to add_conv: the NEXT layer must be an encoder block
+    XfReq xf_req;          // of the layer being built (add_conv fills out / done)
+    bool xf_have = false;  // the previous layer's producer has already written this block's y = FiLM(x_conv(.))
+    Tensor xf_y;
+
+    explicit PlanBuilder(Plan& plan)
+        : p(plan), net(*plan.net), c(plan.net->cfg), train(plan.train_mode), B(plan.B), Cl(c.lms_channel), Pn(c.pan_channel), nlev(c.n_channel_mults), pre(plan.pre),
+          step(plan.step) {}
+
+    const float* V(const std::string& k) const {
+        auto it = net.vec.find(k);
+        return it == net.vec.end() ? nullptr : it->second;
     }
-    for (int l = 0; l < nlev; ++l) {
-        DDIF_TRY(alloc_tensor(&cenc[l], Cl + P, LH[l], LW[l]));
-        DDIF_TRY(alloc_tensor(&cdec[l], Cl + 3 * P, LH[l], LW[l]));
-        for (int which = 0; which < 2; ++which) {
-            Tensor t = which ? cdec[l] : cenc[l];
-            const int cbeg = which ? CC - (Cl + 3 * P) : 0;
+    const PackedConv* PC(const std::string& k) const {
+        auto it = net.conv.find(k);
+        return it == net.conv.end() ? nullptr : &it->second;
+    }
+    int need_conv(const std::string& k, const PackedConv** pc) const {
+        *pc = PC(k);
+        return *pc ? 0 : fail(DDIF_ERR_MISSING, "%s missing", k.c_str());
+    }
+    static int cls_small(int HW, int other) { return HW <= 256 ? 2 : other; }  // profiling class of an elementwise / per-sample launch
+    // train: the record of one module of UNetSR3.forward for the reverse pass (ddif_train.cpp); the caller adds the module-specific tensors
+    Plan::TrainMod& tmod(Plan::TrainMod::Kind kind, const std::string& key, Tensor in, Tensor out) {
+        Plan::TrainMod m;
+        m.kind = kind;
+        m.key = key;
+        m.in = in;
+        m.out = out;
+        p.tmods.push_back(m);
+        return p.tmods.back();
+    }
+
+    // ---- boundary staging + sampler state
+    int boundary_buffers() {
+        const int H = p.H, W = p.W, C = p.C;
+        DDIF_TRY(p.dalloc(&p.zeros, (size_t)1024));
+        if (!p.dry) DDIF_HIPCHK(hipMemset(p.zeros, 0, 1024 * sizeof(float)));
+        DDIF_TRY(p.alloc_tensor(&p.x_in, c.in_channel, H, W));
+        DDIF_TRY(p.alloc_tensor(&p.sc_in, c.out_channel, H, W));
+        DDIF_TRY(p.alloc_tensor(&p.lms, C, H, W));
+        const size_t img_n = (size_t)B * H * W * C;
+        for (int i = 0; i < 2; ++i) DDIF_TRY(p.dalloc(&p.img[i], img_n));
+        for (int i = 0; i < 3; ++i) DDIF_TRY(p.dalloc(&p.mbuf[i], img_n));
+        DDIF_TRY(p.dalloc(&p.io_nchw, (size_t)B * H * W * (c.in_channel > C ? c.in_channel : C)));
+        DDIF_TRY(p.dalloc(&p.small, (size_t)4 * B + 64));
+        return 0;
+    }
+
+    // ---- cond-only program (set_cond): lms and the resized cond images of every level
+    int cond_program() {
+        Plan* const plan = &p;
+        const int H = p.H, W = p.W, CC = p.CC;
+        p.cenc.resize(nlev);
+        p.cdec.resize(nlev);
+        {
             Op op;
-            op.name = "cond_resize";
-            const int BB = B, CCc = CC, HH = H, WW = W;
-            op.bytes = 4.0 * B * t.C * ((double)H * W + (double)t.H * t.W);
-            op.run = [this, t, cbeg, BB, CCc, HH, WW](hipStream_t s, const StepCtx&) {
-                hipLaunchKernelGGL(resize_bilinear_kernel, ew_grid((size_t)BB * t.H * t.W * t.C), dim3(256), 0, s,
-                                   (const float*)this->cond_nchw, BB, CCc, HH, WW, cbeg, t.C, t.H, t.W, t.p);
+            op.name = "lms_nhwc";
+            Tensor lm = p.lms;
+            const int BB = B, CCc = CC, HW = H * W, Cc = p.C;
+            op.run = [plan, lm, BB, CCc, HW, Cc](hipStream_t s, const StepCtx&) {
+                hipLaunchKernelGGL(nchw_to_nhwc_kernel, ew_grid((size_t)BB * HW * Cc), dim3(256), 0, s, (const float*)plan->cond_nchw, BB, CCc, HW, 0, Cc, lm.p);
             };
             pre.push_back(std::move(op));
         }
+        for (int l = 0; l < nlev; ++l) {
+            DDIF_TRY(p.alloc_tensor(&p.cenc[l], Cl + Pn, p.LH[l], p.LW[l]));
+            DDIF_TRY(p.alloc_tensor(&p.cdec[l], Cl + 3 * Pn, p.LH[l], p.LW[l]));
+            for (int which = 0; which < 2; ++which) {
+                Tensor t = which ? p.cdec[l] : p.cenc[l];
+                const int cbeg = which ? CC - (Cl + 3 * Pn) : 0;
+                Op op;
+                op.name = "cond_resize";
+                const int BB = B, CCc = CC, HH = H, WW = W;
+                op.bytes = 4.0 * B * t.C * ((double)H * W + (double)t.H * t.W);
+                op.run = [plan, t, cbeg, BB, CCc, HH, WW](hipStream_t s, const StepCtx&) {
+                    hipLaunchKernelGGL(resize_bilinear_kernel, ew_grid((size_t)BB * t.H * t.W * t.C), dim3(256), 0, s,
+                                       (const float*)plan->cond_nchw, BB, CCc, HH, WW, cbeg, t.C, t.H, t.W, t.p);
+                };
+                pre.push_back(std::move(op));
+            }
+        }
+        return 0;
     }
 
-    // helpers shared by the step program
-    auto resblock = [&](const std::string& rb, Tensor in, Tensor* out, XfReq* xf = nullptr) -> int {
+    // ---- ResnetBlock (sr3_dwt.py:300-330)
+    // train mode: y = silu(GN(x)) * dropout mask is materialised (it is also what wgrad needs), conv2 runs on it
+    int gn_silu_dropout(const std::string& rb, Tensor x, const float* g, const float* bt, Tensor* y) {
+        if (!x.st || !g || !bt) return fail(DDIF_ERR_STATE, "%s: GroupNorm without producer statistics / affine", rb.c_str());
+        p.use(x.p);
+        DDIF_TRY(p.alloc_tensor(y, x.C, x.H, x.W, true));
+        Plan::DropSite site{nullptr, x.C, x.H, x.W};
+        DDIF_TRY(p.dalloc(&site.mask, (size_t)B * x.H * x.W * x.C));
+        p.drop_sites.push_back(site);
+        const int HW = x.H * x.W, Cc = x.C, BB = B;
+        const int chunks = (HW * Cc / 4 + 256 * 8 - 1) / (256 * 8);
+        Tensor yy = *y;
+        Op op;
+        op.name = "gn_silu_dropout";
+        op.cls = cls_small(HW, 5);
+        op.bytes = 12.0 * B * HW * Cc;
+        op.run = [x, g, bt, site, yy, HW, Cc, BB, chunks](hipStream_t s, const StepCtx&) {
+            hipLaunchKernelGGL(gn_silu_drop_kernel, dim3(chunks < 1 ? 1 : chunks, BB), dim3(256), 0, s, (const float*)x.p, (const double*)x.st, x.np, g, bt,
+                               (const float*)site.mask, HW, Cc, yy.p);
+        };
+        step.push_back(std::move(op));
+        return 0;
+    }
+    int resblock(const std::string& rb, Tensor in, Tensor* out, XfReq* xf = nullptr) {
         const PackedConv *c1 = PC(rb + ".block1.block.3"), *c2 = PC(rb + ".block2.block.3");
         if (!c1 || !c2) return fail(DDIF_ERR_MISSING, "%s: conv weights missing", rb.c_str());
         Tensor h1;
-        if (train_mode) {
-            // train mode: y = silu(GN(h1)) * dropout mask is materialised (it is also what wgrad needs), conv2 runs on it
-            auto dropped = [&](Tensor x, const float* g, const float* bt, Tensor* y) -> int {
-                if (!x.st || !g || !bt) return fail(DDIF_ERR_STATE, "%s: GroupNorm without producer statistics / affine", rb.c_str());
-                use(x.p);
-                DDIF_TRY(alloc_tensor(y, x.C, x.H, x.W, true));
-                DropSite site{nullptr, x.C, x.H, x.W};
-                DDIF_TRY(dalloc(&site.mask, (size_t)B * x.H * x.W * x.C));
-                drop_sites.push_back(site);
-                const int HW = x.H * x.W, Cc = x.C, BB = B;
-                const int chunks = (HW * Cc / 4 + 256 * 8 - 1) / (256 * 8);
-                Tensor yy = *y;
-                Op op;
-                op.name = "gn_silu_dropout";
-                op.cls = (HW <= 256) ? 2 : 5;
-                op.bytes = 12.0 * B * HW * Cc;
-                op.run = [x, g, bt, site, yy, HW, Cc, BB, chunks](hipStream_t s, const StepCtx&) {
-                    hipLaunchKernelGGL(gn_silu_drop_kernel, dim3(chunks < 1 ? 1 : chunks, BB), dim3(256), 0, s, (const float*)x.p, (const double*)x.st, x.np, g, bt,
-                                       (const float*)site.mask, HW, Cc, yy.p);
-                };
-                step.push_back(std::move(op));
-                return 0;
-            };
-            // Dropout sits in block2 only (ResnetBlock.__init__, sr3_dwt.py:318-319): block1 keeps the fused GroupNorm + SiLU prologue
-            Tensor y2;
-            ConvSpec s1;
-            s1.pc = c1;
-            s1.in0 = in;
-            s1.pro = PRO_GN_SILU;
-            s1.gamma = V(rb + ".block1.block.0.weight");
-            s1.beta = V(rb + ".block1.block.0.bias");
-            s1.tb_off = net->slot_off.at(rb);
-            s1.stats = true;
-            s1.name = "res.conv1";
-            DDIF_TRY(add_conv(step, s1, &h1));
-            DDIF_TRY(dropped(h1, V(rb + ".block2.block.0.weight"), V(rb + ".block2.block.0.bias"), &y2));
-            ConvSpec s2;
-            s2.pc = c2;
-            s2.in0 = y2;
-            s2.res = in.p;
-            s2.stats = true;
-            s2.name = "res.conv2 (train)";
-            DDIF_TRY(add_conv(step, s2, out));
-            TrainMod m;
-            m.kind = TrainMod::RES;
-            m.key = rb;
-            m.in = in;
-            m.out = *out;
-            m.t[0] = h1;
-            m.t[1] = y2;
-            m.mask = drop_sites.back().mask;
-            m.slot = net->slot_off.at(rb);
-            tmods.push_back(m);
-            return 0;
-        }
         ConvSpec s1;
         s1.pc = c1;
         s1.in0 = in;
         s1.pro = PRO_GN_SILU;
         s1.gamma = V(rb + ".block1.block.0.weight");
         s1.beta = V(rb + ".block1.block.0.bias");
-        s1.tb_off = net->slot_off.at(rb);
+        s1.tb_off = net.slot_off.at(rb);
         s1.stats = true;
         s1.name = "res.conv1";
-        DDIF_TRY(add_conv(step, s1, &h1));
+        DDIF_TRY(p.add_conv(step, s1, &h1));
         ConvSpec s2;
         s2.pc = c2;
-        s2.in0 = h1;
-        s2.pro = PRO_GN_SILU;
-        s2.gamma = V(rb + ".block2.block.0.weight");
-        s2.beta = V(rb + ".block2.block.0.bias");
         s2.res = in.p;
         s2.stats = true;
-        s2.xf = xf;
-        s2.name = "res.conv2";
-        return add_conv(step, s2, out);
-    };
-    auto attention = [&](const std::string& ap, Tensor in, Tensor* out) -> int {
+        if (!train) {
+            s2.in0 = h1;
+            s2.pro = PRO_GN_SILU;
+            s2.gamma = V(rb + ".block2.block.0.weight");
+            s2.beta = V(rb + ".block2.block.0.bias");
+            s2.xf = xf;
+            s2.name = "res.conv2";
+            return p.add_conv(step, s2, out);
+        }
+        // Dropout sits in block2 only (ResnetBlock.__init__, sr3_dwt.py:318-319): block1 keeps the fused GroupNorm + SiLU prologue
+        Tensor y2;
+        DDIF_TRY(gn_silu_dropout(rb, h1, V(rb + ".block2.block.0.weight"), V(rb + ".block2.block.0.bias"), &y2));
+        s2.in0 = y2;
+        s2.name = "res.conv2 (train)";
+        DDIF_TRY(p.add_conv(step, s2, out));
+        Plan::TrainMod& m = tmod(Plan::TrainMod::RES, rb, in, *out);
+        m.t[0] = h1;
+        m.t[1] = y2;
+        m.mask = p.drop_sites.back().mask;
+        m.slot = net.slot_off.at(rb);
+        return 0;
+    }
+
+    // ---- SelfAttention (sr3_dwt.py:333-361)
+    // 64-token tiles: GroupNorm -> qkv -> softmax(q k^T / sqrt(C)) v -> out + bias + x in ONE kernel, one workgroup per sample (kernels_attn.h)
+    int attn_block(const std::string& ap, const PackedConv* cq, const PackedConv* co, Tensor in, Tensor* out) {
+        p.use(in.p);
+        DDIF_TRY(p.alloc_tensor(out, in.C, in.H, in.W, true));
+        const int asplit = attn_block_split();  // workgroups (= statistics partials) per sample
+        out->np = asplit;
+        DDIF_TRY(p.dalloc(&out->st, (size_t)B * 2 * asplit));
+        DDIF_TRY(attn_block_prepare());
+        AttnBlockArgs a{};
+        a.x = in.p;
+        a.st = in.st;
+        a.np = in.np;
+        a.gamma = V(ap + ".norm.weight");
+        a.beta = V(ap + ".norm.bias");
+        a.wqkv = cq->w_x3;
+        {   // qkv on f16x2 (three products) where the f16x2 conditions of a GroupNorm-prologue conv hold: half packs exist (|w| < 64), and the bound
+            // sqrt(N) max|gamma| + max|beta| of GroupNorm's output stays inside the scaled half range; DDIF_ATTN_F16=0 keeps bf16x3 (tests/test_env_switches.py)
+            static const bool af16 = env_flag("DDIF_ATTN_F16", true);
+            auto ig = net.vec_absmax.find(a.gamma), ib = net.vec_absmax.find(a.beta);
+            const bool okr = ig != net.vec_absmax.end() && ib != net.vec_absmax.end() &&
+                             std::sqrt((double)in.C * in.H * in.W) * ig->second + ib->second < DDIF_F16_AMAX;
+            a.wqkv_f16 = (af16 && f16_enabled() && cq->w_f16 && okr) ? cq->w_f16 : nullptr;
+        }
+        a.wout = co->w_x3;
+        a.bout = co->bias ? co->bias : p.zeros;
+        a.scale = 1.0f / std::sqrt((float)in.C);  // 1/sqrt(C), not 1/sqrt(d)   (sr3_dwt.py:352)
+        a.out = out->p;
+        a.st_out = out->st;
+        a.B = B;
+        a.xcd = (xcd_mask() & 8) ? 1 : 0;
+        if (!a.gamma || !a.beta) return fail(DDIF_ERR_MISSING, "%s: norm weights missing", ap.c_str());
+        Op op;
+        op.name = "attn_block";
+        op.label = "attn_block (GN + qkv + attention + out + residual) @8x8";
+        op.cls = 3;
+        op.flop = 2.0 * B * 64 * 128.0 * (384 + 128) + 4.0 * B * 8 * 64.0 * 64 * 16;
+        op.bytes = 8.0 * B * 64 * 128;
+        const int ncu = num_cus();
+        op.run = [a, ncu, asplit](hipStream_t s, const StepCtx&) { attn_block_launch(a, a.B * asplit < ncu ? a.B * asplit : ncu, s); };
+        step.push_back(std::move(op));
+        return 0;
+    }
+    int self_attention(const std::string& ap, Tensor in, Tensor* out) {
         const PackedConv *cq = PC(ap + ".qkv"), *co = PC(ap + ".out");
         if (!cq || !co) return fail(DDIF_ERR_MISSING, "%s: conv weights missing", ap.c_str());
-        if (!train_mode && in.H * in.W == 64 && in.C == 128 && x3_enabled() && lr_enabled() && cq->w_x3 && co->w_x3 && cq->ck == 32 && co->ck == 32 && in.st) {
-            // 64-token tiles: GroupNorm -> qkv -> softmax(q k^T / sqrt(C)) v -> out + bias + x in ONE kernel, one workgroup per
-            // sample (kernels_attn.h); other sizes take the three-launch path below
-            use(in.p);
-            DDIF_TRY(alloc_tensor(out, in.C, in.H, in.W, true));
-            const int asplit = attn_block_split();  // workgroups (= statistics partials) per sample
-            out->np = asplit;
-            DDIF_TRY(dalloc(&out->st, (size_t)B * 2 * asplit));
-            DDIF_TRY(attn_block_prepare());
-            AttnBlockArgs a{};
-            a.x = in.p;
-            a.st = in.st;
-            a.np = in.np;
-            a.gamma = V(ap + ".norm.weight");
-            a.beta = V(ap + ".norm.bias");
-            a.wqkv = cq->w_x3;
-            {   // qkv on f16x2 (three products) where the f16x2 conditions of a GroupNorm-prologue conv hold: half packs exist (|w| < 64), and the bound
-                // sqrt(N) max|gamma| + max|beta| of GroupNorm's output stays inside the scaled half range; DDIF_ATTN_F16=0 keeps bf16x3 (tests/test_env_switches.py)
-                static const bool af16 = [] { const char* e = getenv("DDIF_ATTN_F16"); return !e || atoi(e) != 0; }();
-                auto ig = net->vec_absmax.find(a.gamma), ib = net->vec_absmax.find(a.beta);
-                const bool okr = ig != net->vec_absmax.end() && ib != net->vec_absmax.end() &&
-                                 std::sqrt((double)in.C * in.H * in.W) * ig->second + ib->second < DDIF_F16_AMAX;
-                a.wqkv_f16 = (af16 && f16_enabled() && cq->w_f16 && okr) ? cq->w_f16 : nullptr;
-            }
-            a.wout = co->w_x3;
-            a.bout = co->bias ? co->bias : zeros;
-            a.scale = 1.0f / std::sqrt((float)in.C);  // 1/sqrt(C), not 1/sqrt(d)   (sr3_dwt.py:352)
-            a.out = out->p;
-            a.st_out = out->st;
-            a.B = B;
-            a.xcd = (xcd_mask() & 8) ? 1 : 0;
-            if (!a.gamma || !a.beta) return fail(DDIF_ERR_MISSING, "%s: norm weights missing", ap.c_str());
-            Op op;
-            op.name = "attn_block";
-            op.label = "attn_block (GN + qkv + attention + out + residual) @8x8";
-            op.cls = 3;
-            op.flop = 2.0 * B * 64 * 128.0 * (384 + 128) + 4.0 * B * 8 * 64.0 * 64 * 16;
-            op.bytes = 8.0 * B * 64 * 128;
-            const int ncu = num_cus();
-            op.run = [a, ncu, asplit](hipStream_t s, const StepCtx&) { attn_block_launch(a, a.B * asplit < ncu ? a.B * asplit : ncu, s); };
-            step.push_back(std::move(op));
-            return 0;
-        }
+        if (!train && in.H * in.W == 64 && in.C == 128 && x3_enabled() && lr_enabled() && cq->w_x3 && co->w_x3 && cq->ck == 32 && co->ck == 32 && in.st)
+            return attn_block(ap, cq, co, in, out);
+        // other sizes: three launches
         Tensor qkv, o;
         ConvSpec s1;
         s1.pc = cq;
@@ -781,9 +803,9 @@ int Plan::build_impl() {
         s1.beta = V(ap + ".norm.bias");
         s1.use_bias = false;
         s1.name = "attn.qkv";
-        DDIF_TRY(add_conv(step, s1, &qkv));
-        DDIF_TRY(alloc_tensor(&o, in.C, in.H, in.W, true));
-        use(qkv.p);
+        DDIF_TRY(p.add_conv(step, s1, &qkv));
+        DDIF_TRY(p.alloc_tensor(&o, in.C, in.H, in.W, true));
+        p.use(qkv.p);
         {
             Op op;
             op.name = "self_attn";
@@ -803,29 +825,25 @@ int Plan::build_impl() {
         s2.res = in.p;
         s2.stats = true;
         s2.name = "attn.out";
-        DDIF_TRY(add_conv(step, s2, out));
-        if (train_mode) {
-            TrainMod m;
-            m.kind = TrainMod::ATTN;
-            m.key = ap;
-            m.in = in;
-            m.out = *out;
+        DDIF_TRY(p.add_conv(step, s2, out));
+        if (train) {
+            Plan::TrainMod& m = tmod(Plan::TrainMod::ATTN, ap, in, *out);
             m.t[0] = qkv;
             m.t[1] = o;
-            tmods.push_back(m);
         }
         return 0;
-    };
+    }
+    // ResnetBlocWithAttn's second half: attention on the chain tensor where the layer has one
+    int attention_if(const Layer& L) {
+        if (!L.attn) return 0;
+        Tensor t2;
+        DDIF_TRY(self_attention(L.p + ".attn", cur, &t2));
+        cur = t2;
+        return 0;
+    }
 
-    // ---- step program
-    Tensor cur;
-    std::vector<Tensor> feats;
-    std::vector<int> feat_mod;  // train: index in tmods of the module that produced each feature
-    int lev = 0;
-    // cond-only FiLM branch of an encoder block: body(cond) -> scale | shift (sr3_dwt.py:379-391); built when first asked for -- by the block itself, or one
-    // layer earlier by the conv that folds the block's x_conv + FiLM into its epilogue (round 6)
-    std::map<const Layer*, std::pair<Tensor, Tensor>> film_cache;  // block -> (hid, film)
-    auto film_of = [&](const Layer& Lb, int at_lev, Tensor* hid_out, Tensor* film_out) -> int {
+    // ---- encoder
+    int film_of(const Layer& Lb, int at_lev, Tensor* hid_out, Tensor* film_out) {
         auto it = film_cache.find(&Lb);
         if (it != film_cache.end()) {
             *hid_out = it->second.first;
@@ -835,35 +853,31 @@ int Plan::build_impl() {
         const std::string ci = Lb.p + ".cond_inj";
         Tensor hid, film;
         ConvSpec s;
-        s.pc = PC(ci + ".body.0");
-        if (!s.pc) return fail(DDIF_ERR_MISSING, "%s.body.0 missing", ci.c_str());
-        s.in0 = cenc[at_lev];
+        DDIF_TRY(need_conv(ci + ".body.0", &s.pc));
+        s.in0 = p.cenc[at_lev];
         s.use_bias = false;
         s.stats = true;
         s.name = "film.body0";
-        DDIF_TRY(add_conv(pre, s, &hid));
+        DDIF_TRY(p.add_conv(pre, s, &hid));
         ConvSpec s2;
-        s2.pc = PC(ci + ".body.3");
-        if (!s2.pc) return fail(DDIF_ERR_MISSING, "%s.body.3 missing", ci.c_str());
+        DDIF_TRY(need_conv(ci + ".body.3", &s2.pc));
         s2.in0 = hid;
         s2.pro = PRO_GN_SILU;
         s2.gamma = V(ci + ".body.1.weight");
         s2.beta = V(ci + ".body.1.bias");
         s2.name = "film.body3";
-        DDIF_TRY(add_conv(pre, s2, &film));
+        DDIF_TRY(p.add_conv(pre, s2, &film));
         film_cache[&Lb] = std::make_pair(hid, film);
         *hid_out = hid;
         *film_out = film;
         return 0;
-    };
-    // the fold request a producer conv at index li (stem / Downsample / the last conv of a block) hands to add_conv: the NEXT layer must be an encoder block
-    XfReq xf_req;           // of the layer being built (add_conv fills out / done)
-    bool xf_have = false;   // the previous layer's producer has already written this block's y = FiLM(x_conv(.))
-    Tensor xf_y;
-    auto xf_prepare = [&](size_t li, int next_lev) -> int {
+    }
+    // fold-request bookkeeping around a producer conv: fold_begin() resets xf_req and, where the layer after downs[li] (at level next_lev) is an encoder block
+    // with a register-GEMM pack, fills it in; the producer's ConvSpec::xf points at xf_req; fold_end() notes whether add_conv honoured it
+    int fold_begin(size_t li, int next_lev, bool may_fold = true) {
         xf_req = XfReq();
-        if (train_mode || li + 1 >= net->downs.size()) return 0;
-        const Layer& Ln = net->downs[li + 1];
+        if (!may_fold || train || li + 1 >= net.downs.size()) return 0;
+        const Layer& Ln = net.downs[li + 1];
         if (Ln.kind == L_STEM || Ln.kind == L_DOWN) return 0;
         const std::string ci = Ln.p + ".cond_inj";
         const PackedConv* px = PC(ci + ".x_conv");
@@ -875,586 +889,541 @@ int Plan::build_impl() {
         xf_req.w = wxf;
         xf_req.film = film.p;
         return 0;
-    };
-    for (size_t li = 0; li < net->downs.size(); ++li) {
-        auto& L = net->downs[li];
-        if (L.kind == L_STEM) {
-            const PackedConv* pc = PC(L.p);
-            if (!pc) return fail(DDIF_ERR_MISSING, "%s missing", L.p.c_str());
-            ConvSpec s;
-            s.pc = pc;
-            s.dyn_input = true;
-            if (c.self_condition) {
-                s.in0 = sc_in;
-                s.in1 = x_in;
-            } else {
-                s.in0 = x_in;
-            }
-            s.stats = true;
-            s.name = "stem";
-            DDIF_TRY(xf_prepare(li, lev));
-            s.xf = &xf_req;
-            DDIF_TRY(add_conv(step, s, &cur));
-            xf_have = xf_req.done;
-            xf_y = xf_req.out;
-            if (train_mode) {
-                TrainMod m;
-                m.kind = TrainMod::STEM;
-                m.key = L.p;
-                m.out = cur;
-                tmods.push_back(m);
-            }
-        } else if (L.kind == L_DOWN) {
-            ConvSpec s;
-            s.pc = PC(L.p + ".conv");
-            if (!s.pc) return fail(DDIF_ERR_MISSING, "%s.conv missing", L.p.c_str());
-            s.in0 = cur;
-            s.stride = 2;
-            s.stats = true;
-            s.name = "down";
-            const Tensor din = cur;
-            DDIF_TRY(xf_prepare(li, lev + 1));
-            s.xf = &xf_req;
-            DDIF_TRY(add_conv(step, s, &cur));
-            xf_have = xf_req.done;
-            xf_y = xf_req.out;
-            ++lev;
-            if (train_mode) {
-                TrainMod m;
-                m.kind = TrainMod::DOWN;
-                m.key = L.p + ".conv";
-                m.in = din;
-                m.out = cur;
-                tmods.push_back(m);
-            }
+    }
+    void fold_end() {
+        xf_have = xf_req.done;
+        xf_y = xf_req.out;
+    }
+    int stem(size_t li) {
+        const Layer& L = net.downs[li];
+        const PackedConv* pc = PC(L.p);
+        if (!pc) return fail(DDIF_ERR_MISSING, "%s missing", L.p.c_str());
+        ConvSpec s;
+        s.pc = pc;
+        s.dyn_input = true;
+        if (c.self_condition) {
+            s.in0 = p.sc_in;
+            s.in1 = p.x_in;
         } else {
-            const std::string ci = L.p + ".cond_inj";
-            // cond-only: body(cond) -> FiLM scale|shift   (sr3_dwt.py:379-391)
-            Tensor hid, film;
-            DDIF_TRY(film_of(L, lev, &hid, &film));
-            Tensor y;
-            const bool y_folded = xf_have;  // the producer one layer up wrote y already (EPI_XF)
-            xf_have = false;
-            ConvSpec s;
-            s.pc = PC(ci + ".x_conv");
-            if (!s.pc) return fail(DDIF_ERR_MISSING, "%s.x_conv missing", ci.c_str());
-            s.in0 = cur;
-            if (train_mode) {
-                // train: xc = x_conv(x) is kept (FiLM's backward needs it), the modulation is a launch of its own
-                Tensor xc;
-                s.name = "film.x_conv (train)";
-                DDIF_TRY(add_conv(step, s, &xc));
-                DDIF_TRY(alloc_tensor(&y, xc.C, xc.H, xc.W, true));
-                const int HWl = xc.H * xc.W, Cc = xc.C, BB = B;
-                const int chunks = tk::film_chunks(HWl, Cc);
-                y.np = chunks;
-                DDIF_TRY(dalloc(&y.st, (size_t)B * chunks * 2));
-                Tensor yy = y;
-                Op op;
-                op.name = "film_apply";
-                op.cls = (HWl <= 256) ? 2 : 5;
-                op.bytes = 16.0 * B * HWl * Cc;
-                op.run = [xc, film, yy, HWl, Cc, BB, chunks](hipStream_t st, const StepCtx&) {
-                    tk::film_apply(st, xc.p, film.p, BB, HWl, Cc, yy.p, yy.st, chunks);
-                };
-                step.push_back(std::move(op));
-                // the cond image zero-padded to 4 | channels: input of body.0's weight gradient (cond-only, part of set_cond)
-                if ((int)cenc_pad.size() < nlev) cenc_pad.resize(nlev);
-                if (!cenc_pad[lev].p) {
-                    const int Cp = (cenc[lev].C + 3) & ~3;
-                    DDIF_TRY(alloc_tensor(&cenc_pad[lev], Cp, cenc[lev].H, cenc[lev].W));
-                }
-                TrainMod m;
-                m.kind = TrainMod::FILM;
-                m.key = ci;
-                m.in = cur;
-                m.out = y;
-                m.t[0] = xc;
-                m.t[1] = film;
-                m.t[2] = hid;
-                m.t[3] = cenc[lev];
-                m.t[4] = cenc_pad[lev];
-                m.lev = lev;
-                tmods.push_back(m);
-            } else if (y_folded) {
-                y = xf_y;
-            } else {
+            s.in0 = p.x_in;
+        }
+        s.stats = true;
+        s.name = "stem";
+        DDIF_TRY(fold_begin(li, lev));
+        s.xf = &xf_req;
+        DDIF_TRY(p.add_conv(step, s, &cur));
+        fold_end();
+        if (train) tmod(Plan::TrainMod::STEM, L.p, Tensor(), cur);
+        return 0;
+    }
+    int down(size_t li) {
+        const Layer& L = net.downs[li];
+        ConvSpec s;
+        DDIF_TRY(need_conv(L.p + ".conv", &s.pc));
+        s.in0 = cur;
+        s.stride = 2;
+        s.stats = true;
+        s.name = "down";
+        const Tensor din = cur;
+        DDIF_TRY(fold_begin(li, lev + 1));
+        s.xf = &xf_req;
+        DDIF_TRY(p.add_conv(step, s, &cur));
+        fold_end();
+        ++lev;
+        if (train) tmod(Plan::TrainMod::DOWN, L.p + ".conv", din, cur);
+        return 0;
+    }
+    // train: xc = x_conv(x) is kept (FiLM's backward needs it), the modulation is a launch of its own
+    int cond_injection_train(const std::string& ci, ConvSpec& s, Tensor hid, Tensor film, Tensor* y_out) {
+        Tensor xc, y;
+        s.name = "film.x_conv (train)";
+        DDIF_TRY(p.add_conv(step, s, &xc));
+        DDIF_TRY(p.alloc_tensor(&y, xc.C, xc.H, xc.W, true));
+        const int HWl = xc.H * xc.W, Cc = xc.C, BB = B;
+        const int chunks = tk::film_chunks(HWl, Cc);
+        y.np = chunks;
+        DDIF_TRY(p.dalloc(&y.st, (size_t)B * chunks * 2));
+        Tensor yy = y;
+        Op op;
+        op.name = "film_apply";
+        op.cls = cls_small(HWl, 5);
+        op.bytes = 16.0 * B * HWl * Cc;
+        op.run = [xc, film, yy, HWl, Cc, BB, chunks](hipStream_t st, const StepCtx&) { tk::film_apply(st, xc.p, film.p, BB, HWl, Cc, yy.p, yy.st, chunks); };
+        step.push_back(std::move(op));
+        // the cond image zero-padded to 4 | channels: input of body.0's weight gradient (cond-only, part of set_cond)
+        if ((int)p.cenc_pad.size() < nlev) p.cenc_pad.resize(nlev);
+        if (!p.cenc_pad[lev].p) {
+            const int Cp = (p.cenc[lev].C + 3) & ~3;
+            DDIF_TRY(p.alloc_tensor(&p.cenc_pad[lev], Cp, p.cenc[lev].H, p.cenc[lev].W));
+        }
+        Plan::TrainMod& m = tmod(Plan::TrainMod::FILM, ci, cur, y);
+        m.t[0] = xc;
+        m.t[1] = film;
+        m.t[2] = hid;
+        m.t[3] = p.cenc[lev];
+        m.t[4] = p.cenc_pad[lev];
+        m.lev = lev;
+        *y_out = y;
+        return 0;
+    }
+    // CondInjection (y = FiLM(x_conv(x)), sr3_dwt.py:379-391) + ResnetBlocWithAttn
+    int encoder_block(size_t li) {
+        const Layer& L = net.downs[li];
+        const std::string ci = L.p + ".cond_inj";
+        // cond-only: body(cond) -> FiLM scale|shift
+        Tensor hid, film;
+        DDIF_TRY(film_of(L, lev, &hid, &film));
+        Tensor y;
+        const bool y_folded = xf_have;  // the producer one layer up wrote y already (EPI_XF)
+        xf_have = false;
+        ConvSpec s;
+        DDIF_TRY(need_conv(ci + ".x_conv", &s.pc));
+        s.in0 = cur;
+        if (train) {
+            DDIF_TRY(cond_injection_train(ci, s, hid, film, &y));
+        } else if (y_folded) {
+            y = xf_y;
+        } else {
             s.film = film.p;
             s.stats = true;
             s.name = "film.x_conv";
-            DDIF_TRY(add_conv(step, s, &y));
-            }
-            // the block's last conv folds the NEXT block's x_conv + FiLM when nothing (attention) sits between them
-            xf_req = XfReq();
-            if (!L.attn) DDIF_TRY(xf_prepare(li, lev));
-            DDIF_TRY(resblock(L.p + ".res_block", y, &cur, (!train_mode && !L.attn) ? &xf_req : nullptr));
-            xf_have = xf_req.done;
-            xf_y = xf_req.out;
-            if (L.attn) {
-                Tensor t2;
-                DDIF_TRY(attention(L.p + ".attn", cur, &t2));
-                cur = t2;
-            }
+            DDIF_TRY(p.add_conv(step, s, &y));
         }
-        feats.push_back(cur);
-        if (train_mode) {
-            tmods.back().pushes_feat = true;
-            feat_mod.push_back((int)tmods.size() - 1);
-        }
+        // the block's last conv folds the NEXT block's x_conv + FiLM when nothing (attention) sits between them
+        DDIF_TRY(fold_begin(li, lev, !L.attn));
+        DDIF_TRY(resblock(L.p + ".res_block", y, &cur, (!train && !L.attn) ? &xf_req : nullptr));
+        fold_end();
+        return attention_if(L);
     }
-    for (auto& L : net->mid) {
+    int mid_block(const Layer& L) {
         Tensor t1;
         DDIF_TRY(resblock(L.p + ".res_block", cur, &t1));
         cur = t1;
-        if (L.attn) {
-            Tensor t2;
-            DDIF_TRY(attention(L.p + ".attn", cur, &t2));
-            cur = t2;
-        }
+        return attention_if(L);
     }
-    if (train_mode) {  // the decoder-only half of the cond-only program ran on the side stream (set_cond): it must be complete from here on
+    // train: the decoder-only half of the cond-only program ran on the side stream (set_cond): it must be complete from here on
+    void join_side_stream() {
+        Plan* const plan = &p;
         Op j;
         j.name = "join cond-only side work";
-        j.run = [this](hipStream_t s, const StepCtx&) {  // (not under a stream capture: the samplers join before they start capturing)
-            if (this->side_pending) {
-                this->train_join(s);
-                this->side_pending = false;
+        j.run = [plan](hipStream_t s, const StepCtx&) {  // (not under a stream capture: the samplers join before they start capturing)
+            if (plan->side_pending) {
+                plan->train_join(s);
+                plan->side_pending = false;
             }
         };
         step.push_back(std::move(j));
     }
-    for (auto& L : net->ups) {
-        if (L.kind == L_UP) {
-            ConvSpec s;
-            s.pc = PC(L.p + ".conv");
-            if (!s.pc) return fail(DDIF_ERR_MISSING, "%s.conv missing", L.p.c_str());
-            s.in0 = cur;
-            s.ups = 1;
-            s.stats = true;
-            s.name = "up";
-            const Tensor uin = cur;
-            DDIF_TRY(add_conv(step, s, &cur));
-            --lev;
-            if (train_mode) {
-                TrainMod m;
-                m.kind = TrainMod::UP;
-                m.key = L.p + ".conv";
-                m.in = uin;
-                m.out = cur;
-                tmods.push_back(m);
-            }
-            continue;
-        }
-        const std::string ci = L.p + ".cond_inj";
-        Tensor skip = feats.back();
-        feats.pop_back();
-        int skip_from = -1;
-        if (train_mode) {
-            skip_from = feat_mod.back();
-            feat_mod.pop_back();
-        }
-        if (skip.C != L.cskip || cur.C != L.cx || skip.H != cur.H || skip.W != cur.W)
-            return fail(DDIF_ERR_INVALID, "%s: skip/feature shape mismatch", L.p.c_str());
-        const int fea = L.cin, d = fea / 8, Hl = cur.H, Wl = cur.W, BB = B;
-        const int cd = Cl + 3 * P;
-        // ---- cond-only: kv -> softmax_W(k) -> context   (sr3_dwt.py:514-517,541,546,563)
-        const size_t pre_dec0 = pre.size();  // train: everything this block adds to the cond-only program is decoder-only -> the side stream
-        float* ctx = nullptr;
+
+    // ---- decoder
+    int up(const Layer& L) {
+        ConvSpec s;
+        DDIF_TRY(need_conv(L.p + ".conv", &s.pc));
+        s.in0 = cur;
+        s.ups = 1;
+        s.stats = true;
+        s.name = "up";
+        const Tensor uin = cur;
+        DDIF_TRY(p.add_conv(step, s, &cur));
+        --lev;
+        if (train) tmod(Plan::TrainMod::UP, L.p + ".conv", uin, cur);
+        return 0;
+    }
+    // what the stages of one FastAttnCondInjection block (sr3_dwt.py:495-577) share
+    struct Dec {
+        std::string ci;  // "<block>.cond_inj"
+        Tensor skip;
+        int skip_from = -1;  // train: index in tmods of the module that produced `skip`
+        int fea = 0, d = 0, Hl = 0, Wl = 0, cd = 0;
+        size_t pre_dec0 = 0;  // train: everything this block adds to the cond-only program from here on is decoder-only -> the side stream
+        float* ctx = nullptr;  // inference: linear-attention context [B][8][d][d]
         Tensor kdw, kv;
+        const float *pn_g = nullptr, *pn_b = nullptr, *q0w = nullptr;  // prenorm_x affine, q.0 depthwise weights
+    };
+    // ---- cond-only: kv -> softmax_W(k) -> context   (sr3_dwt.py:514-517,541,546,563)
+    int decoder_context(Dec& D) {
+        const int BB = B, fea = D.fea, d = D.d, Hl = D.Hl, Wl = D.Wl, cd = D.cd;
+        D.pre_dec0 = pre.size();
+        DDIF_TRY(p.alloc_tensor(&D.kdw, cd, Hl, Wl));
         {
-            DDIF_TRY(alloc_tensor(&kdw, cd, Hl, Wl));
-            {
-                DwArgs a{};
-                a.in0 = cdec[lev].p;
-                a.c0 = cd;
-                a.B = B;
-                a.H = Hl;
-                a.W = Wl;
-                a.w = V(ci + ".kv.0.weight");
-                if (!a.w) return fail(DDIF_ERR_MISSING, "%s.kv.0.weight missing", ci.c_str());
-                a.out_dw = kdw.p;
-                a.tiles_x = (Wl + 15) / 16;
-                a.tiles_y = (Hl + 7) / 8;
-                Op op;
-                op.name = "kv.dw3x3";
-                op.flop = 2.0 * 9 * B * Hl * Wl * cd;
-                op.bytes = 8.0 * B * Hl * Wl * cd;
-                op.run = [a, BB](hipStream_t s, const StepCtx&) {
-                    launch_dw3x3(s, a);
-                };
-                pre.push_back(std::move(op));
-            }
-            ConvSpec s;
-            s.pc = PC(ci + ".kv.1");
-            if (!s.pc) return fail(DDIF_ERR_MISSING, "%s.kv.1 missing", ci.c_str());
-            s.in0 = kdw;
-            s.name = "kv.1x1";
-            DDIF_TRY(add_conv(pre, s, &kv));
-            float *kmx = nullptr, *ksm = nullptr;
-            if (!train_mode) {
-            DDIF_TRY(dalloc(&kmx, (size_t)B * Hl * fea));
-            DDIF_TRY(dalloc(&ksm, (size_t)B * Hl * fea));
-            DDIF_TRY(dalloc(&ctx, (size_t)B * 8 * d * d));
-            {
-                Op op;
-                op.name = "k.softmax_stats";
-                op.bytes = 8.0 * B * Hl * Wl * fea;
-                op.run = [kv, kmx, ksm, fea, BB, Hl, Wl](hipStream_t s, const StepCtx&) {
-                    hipLaunchKernelGGL(softmax_stats_kernel, ew_grid((size_t)BB * Hl * fea), dim3(256), 0, s, (const float*)kv.p, 2 * fea, 0, fea, BB, Hl, Wl, 1, kmx, ksm);
-                };
-                pre.push_back(std::move(op));
-            }
-            {
-                Op op;
-                op.name = "linattn_ctx";
-                op.flop = 2.0 * B * 8 * d * d * (double)Hl * Wl;
-                op.bytes = 4.0 * B * Hl * Wl * 2.0 * fea;
-                op.run = [kv, kmx, ksm, ctx, fea, d, BB, Hl, Wl](hipStream_t s, const StepCtx&) {
-                    hipLaunchKernelGGL(linattn_ctx_kernel, dim3(8, BB), dim3(256), 2 * 32 * d * sizeof(float), s, (const float*)kv.p, (const float*)kmx, (const float*)ksm, BB, Hl, Wl, fea, d, ctx);
-                };
-                pre.push_back(std::move(op));
-            }
-            }  // !train_mode (the train-mode forward runs the attention core itself)
-        }
-        if (train_mode) {
-            // ---- train mode: the block op by op (models/sr3_dwt.py:536-577), every intermediate the reverse pass needs kept in memory:
-            //   xn = GN(cat[h, skip]), dwq = dw3x3(xn)        one launch (dw3x3_kernel, two sources, GroupNorm from the producers' partials)
-            //   q = q.1(dwq);  o = linear attention(q, kv)     (kv comes from set_cond);  a = attn_out(o) + attn_res(xn)  as one 1x1 conv over cat[o, xn]
-            //   f0 = ffn.0(a); f1 = silu(f0); f2 = ffn.2(f1); f3c = ffn.3(f2) + b;  out = a + DropPath(f3c)
-            const PackedConv* pq1t = PC(ci + ".q.1");
-            const PackedConv* pmixt = PC(ci + ".attn_mix");
-            if (!pq1t || !pmixt) return fail(DDIF_ERR_MISSING, "%s: q.1 / attn_out missing", ci.c_str());
-            if (!cur.st || !skip.st) return fail(DDIF_ERR_STATE, "%s: prenorm without producer statistics", ci.c_str());
-            const float *pn_g = V(ci + ".prenorm_x.weight"), *pn_b = V(ci + ".prenorm_x.bias"), *q0w = V(ci + ".q.0.weight");
-            if (!pn_g || !pn_b || !q0w) return fail(DDIF_ERR_MISSING, "%s: prenorm/q.0 weights missing", ci.c_str());
-            Tensor xn, dwq, q, o, a, f0, f1, f2, f3c, f3, kdw_pad;
-            float *la_ctx = nullptr, *la_part = nullptr;
-            DDIF_TRY(alloc_tensor(&xn, fea, Hl, Wl, true));
-            DDIF_TRY(alloc_tensor(&dwq, fea, Hl, Wl, true));
-            {
-                DwArgs da{};
-                da.in0 = cur.p;
-                da.c0 = cur.C;
-                da.in1 = skip.p;
-                da.c1 = skip.C;
-                da.B = B;
-                da.H = Hl;
-                da.W = Wl;
-                da.st0 = cur.st;
-                da.np0 = cur.np;
-                da.st1 = skip.st;
-                da.np1 = skip.np;
-                da.gamma = pn_g;
-                da.beta = pn_b;
-                da.w = q0w;
-                da.out_dw = dwq.p;
-                da.out_xn = xn.p;
-                da.use_gn = 1;
-                da.tiles_x = (Wl + 15) / 16;
-                da.tiles_y = (Hl + 7) / 8;
-                Op op;
-                op.name = "q.gn_dw3x3 (train)";
-                op.cls = (Hl * Wl <= 256) ? 2 : 5;
-                op.flop = 2.0 * 9 * B * Hl * Wl * fea;
-                op.bytes = 12.0 * B * Hl * Wl * fea;
-                op.run = [da, BB](hipStream_t s, const StepCtx&) {
-                    launch_dw3x3(s, da);
-                };
-                step.push_back(std::move(op));
-            }
-            {
-                ConvSpec s;
-                s.pc = pq1t;
-                s.in0 = dwq;
-                s.name = "q.1x1 (train)";
-                DDIF_TRY(add_conv(step, s, &q));
-            }
-            DDIF_TRY(alloc_tensor(&o, fea, Hl, Wl, true));
-            {
-                Op op;
-                op.name = "linattn_fwd";
-                op.cls = (Hl * Wl <= 256) ? 2 : 5;
-                op.flop = 4.0 * B * 8 * d * d * (double)Hl * Wl;
-                op.bytes = 16.0 * B * Hl * Wl * fea;
-                Tensor qq = q, kk = kv, oo = o;
-                if ((Hl > Wl ? Hl : Wl) * fea > 8192 || d > 32 || d % 4)
-                    return fail(DDIF_ERR_INVALID, "%s: train-mode linear attention holds one image line x %d channels in LDS: lines of more than %d pixels are not supported",
-                                ci.c_str(), fea, 8192 / fea);
-                DDIF_TRY(dalloc(&la_ctx, (size_t)B * fea * d));
-                DDIF_TRY(dalloc(&la_part, tk::linattn_part_floats(B, Hl, Wl, fea, d)));
-                float *cx = la_ctx, *pt = la_part;
-                {   // cond-only half: softmax_W(k), context = k v^T per head (sr3_dwt.py:541,546,563) -- part of set_cond, like the eval plan's
-                    Op pc;
-                    pc.name = "linattn_ctx (train)";
-                    pc.bytes = 8.0 * B * Hl * Wl * fea;
-                    pc.run = [kk, BB, d, Hl, Wl, cx, pt](hipStream_t s, const StepCtx&) { tk::linattn_ctx(s, kk.p, BB, 8, d, Hl, Wl, cx, pt); };
-                    pre.push_back(std::move(pc));
-                    for (size_t i = pre_dec0; i < pre.size(); ++i) pre[i].side = true;
-                }
-                op.run = [qq, oo, BB, d, Hl, Wl, fea, cx](hipStream_t s, const StepCtx&) { tk::linattn_apply(s, qq.p, cx, BB, 8, d, Hl, Wl, oo.p, fea); };
-                step.push_back(std::move(op));
-            }
-            const bool has_res = pmixt->cin == 2 * fea;
-            {
-                ConvSpec s;
-                s.pc = pmixt;
-                s.in0 = o;
-                if (has_res) s.in1 = xn;
-                else s.res = xn.p;  // attn_res is Identity
-                s.name = "attn_out+res (train)";
-                DDIF_TRY(add_conv(step, s, &a));
-            }
-            {
-                ConvSpec s;
-                s.pc = PC(ci + ".ffn.0");
-                if (!s.pc) return fail(DDIF_ERR_MISSING, "%s.ffn.0 missing", ci.c_str());
-                s.in0 = a;
-                s.use_bias = false;
-                s.name = "ffn.0 (train)";
-                DDIF_TRY(add_conv(step, s, &f0));
-                DDIF_TRY(alloc_tensor(&f1, f0.C, f0.H, f0.W, true));
-                Op op;
-                op.name = "silu";
-                op.cls = (Hl * Wl <= 256) ? 2 : 5;
-                op.bytes = 8.0 * B * Hl * Wl * f0.C;
-                Tensor ff0 = f0, ff1 = f1;
-                const size_t n = (size_t)B * Hl * Wl * f0.C;
-                op.run = [ff0, ff1, n](hipStream_t st, const StepCtx&) { tk::silu_fwd(st, ff0.p, n, ff1.p); };
-                step.push_back(std::move(op));
-                ConvSpec s2;
-                s2.pc = PC(ci + ".ffn.2");
-                if (!s2.pc) return fail(DDIF_ERR_MISSING, "%s.ffn.2 missing", ci.c_str());
-                s2.in0 = f1;
-                s2.use_bias = false;
-                s2.name = "ffn.2 (train)";
-                DDIF_TRY(add_conv(step, s2, &f2));
-                ConvSpec s3;
-                s3.pc = PC(ci + ".ffn.3");
-                if (!s3.pc) return fail(DDIF_ERR_MISSING, "%s.ffn.3 missing", ci.c_str());
-                s3.in0 = f2;
-                s3.name = "ffn.3 (train)";
-                DDIF_TRY(add_conv(step, s3, &f3c));
-            }
-            float* scale = nullptr;
-            {
-                DDIF_TRY(alloc_tensor(&f3, f3c.C, f3c.H, f3c.W, true));
-                DDIF_TRY(dalloc(&scale, (size_t)B));
-                path_sites.push_back(scale);
-                const int HW = f3c.H * f3c.W, Cc = f3c.C;
-                int chunks = (HW * Cc / 4 + 256 * 8 - 1) / (256 * 8);
-                if (chunks < 1) chunks = 1;
-                f3.np = chunks;
-                DDIF_TRY(dalloc(&f3.st, (size_t)B * chunks * 2));
-                Tensor fo = f3, fc = f3c, aa = a;
-                Op op;
-                op.name = "droppath_add";
-                op.cls = (HW <= 256) ? 2 : 5;
-                op.bytes = 12.0 * B * HW * Cc;
-                op.run = [fc, scale, aa, fo, HW, Cc, BB, chunks](hipStream_t s, const StepCtx&) {
-                    hipLaunchKernelGGL(droppath_add_kernel, dim3(chunks, BB), dim3(256), 64, s, (const float*)fc.p, (const float*)scale, (const float*)aa.p, HW, Cc, fo.p, fo.st);
-                };
-                step.push_back(std::move(op));
-            }
-            // kv.0's output zero-padded to 4 | channels: input of kv.1's weight gradient (cond-only)
-            {
-                const int Cp = (cd + 3) & ~3;
-                DDIF_TRY(alloc_tensor(&kdw_pad, Cp, Hl, Wl));
-            }
-            TrainMod m;
-            m.kind = TrainMod::DEC;
-            m.key = ci;
-            m.in = cur;
-            m.out = f3;
-            m.t[0] = skip;
-            m.t[1] = xn;
-            m.t[2] = dwq;
-            m.t[3] = q;
-            m.t[4] = kv;
-            m.t[5] = kdw;
-            m.t[6] = kdw_pad;
-            m.t[7] = o;
-            m.t[8] = a;
-            m.t[9] = f0;
-            m.t[10] = f1;
-            m.t[11] = f2;
-            m.scale = scale;
-            m.ctx = la_ctx;
-            m.la_part = la_part;
-            m.has_res = has_res;
-            m.skip_from = skip_from;
-            m.lev = lev;
-            tmods.push_back(m);
-            // f3c is only needed by the reverse pass through DropPath's scale: d(f3c) = scale * d(out); not stored in the record
-            DDIF_TRY(resblock(L.p + ".res_block", f3, &cur));
-            if (L.attn) {
-                Tensor t2;
-                DDIF_TRY(attention(L.p + ".attn", cur, &t2));
-                cur = t2;
-            }
-            continue;
-        }
-        // ---- per step
-        Tensor xn, q, amix, f1, f2, f3;
-        const PackedConv* pq1 = PC(ci + ".q.1");
-        if (!pq1) return fail(DDIF_ERR_MISSING, "%s.q.1 missing", ci.c_str());
-        if (!cur.st || !skip.st) return fail(DDIF_ERR_STATE, "%s: prenorm without producer statistics", ci.c_str());
-        const float *pn_g = V(ci + ".prenorm_x.weight"), *pn_b = V(ci + ".prenorm_x.bias"), *q0w = V(ci + ".q.0.weight");
-        if (!pn_g || !pn_b || !q0w) return fail(DDIF_ERR_MISSING, "%s: prenorm/q.0 weights missing", ci.c_str());
-        // ---- the whole attention half in ONE launch where the level keeps whole image columns inside a workgroup (kernels_lafuse.h):
-        //      xn = GN(cat[h, skip]) -> q = q.1(q.0(xn)) -> softmax over H -> M_b p + W_res xn + bias; q and xn never reach memory
-        bool fused_attn = false;
-        {
-            const PackedConv* pm = PC(ci + ".attn_mix");
-            const float* wr = V(ci + ".attn_res.weight");
-            // (round 6) the 8 x 8 level has a kernel of its own: half a sample per workgroup, the waves split the output channels (kernels_lafuse8.h)
-            const bool la8 = la8_enabled() && lafuse8_supported(Hl, Wl, cur.C, skip.C, pm ? pm->cout : 0);
-            bool ok = lafuse_enabled() && f16_enabled() && x3_enabled() && lr_enabled() && pm && wr && pq1->w_f16 && pq1->bias && pm->bias && (Hl * Wl >= 256 || la8) &&
-                      pq1->cout == fea && pq1->ck == 32 && pm->ck == 32 && pm->cin == 2 * fea && cur.C % 16 == 0 && skip.C % 16 == 0 && (la8 || lafuse_supported(Hl, fea, pm->cout));
-            if (ok) {  // f16x2 range of depthwise(GroupNorm(.)): (sqrt(N) max|gamma| + max|beta|) * 9 max|w_dw| inside the scaled half range
-                auto ig = net->vec_absmax.find(pn_g), ib = net->vec_absmax.find(pn_b), iw = net->vec_absmax.find(q0w);
-                ok = ig != net->vec_absmax.end() && ib != net->vec_absmax.end() && iw != net->vec_absmax.end() &&
-                     (std::sqrt((double)fea * Hl * Wl) * ig->second + ib->second) * 9.0 * iw->second < DDIF_F16_AMAX;
-            }
-            if (ok) {
-                const float* wo = V(ci + ".attn_out.weight");
-                if (!wo) return fail(DDIF_ERR_MISSING, "%s.attn_out.weight missing", ci.c_str());
-                const int nb_pad = (((pm->cout + 31) / 32) + 3) & ~3;
-                const size_t per = (size_t)nb_pad * pm->n_chunks * 2 * 3 * 256;  // bf16x3 planes, 32-channel chunks
-                float* wmix = nullptr;
-                DDIF_TRY(dalloc(&wmix, per * B));
-                {
-                    Op op;
-                    op.name = "pack_mix_weights";
-                    const float scale = 1.0f / std::sqrt((float)d);
-                    const int co_n = pm->cout, nch = pm->n_chunks;
-                    op.flop = 2.0 * B * co_n * (double)fea * d;
-                    op.run = [wo, wr, ctx, wmix, BB, co_n, fea, d, scale, nch, nb_pad, per](hipStream_t s, const StepCtx&) {
-                        hipLaunchKernelGGL(pack_mix_weights_x3_kernel, ew_grid(per * BB), dim3(256), 0, s, wo, wr, (const float*)ctx, BB, co_n, fea, d, scale, 32, nch, nb_pad, wmix);
-                    };
-                    pre.push_back(std::move(op));
-                }
-                use(cur.p);
-                use(skip.p);
-                DDIF_TRY(alloc_tensor(&amix, pm->cout, Hl, Wl, true));
-                LaFuseArgs a{};
-                a.xcd = (xcd_mask() & 4) ? 1 : 0;
-                a.in0 = cur.p;
-                a.c0 = cur.C;
-                a.in1 = skip.p;
-                a.c1 = skip.C;
-                a.B = B;
-                a.H = Hl;
-                a.W = Wl;
-                a.st0 = cur.st;
-                a.np0 = cur.np;
-                a.st1 = skip.st;
-                a.np1 = skip.np;
-                a.gamma = pn_g;
-                a.beta = pn_b;
-                a.dw_w = q0w;
-                a.wq = pq1->w_f16;
-                a.nchq = pq1->n_chunks;
-                a.bq = pq1->bias;
-                a.wmix = wmix;
-                a.wmix_bstride = (long long)per;
-                a.nch_mix = pm->n_chunks;
-                a.bias = pm->bias;
-                a.out = amix.p;
-                a.dout = pm->cout;
-                // four-wave workgroups of 128 pixels instead of eight-wave ones of 256 when the latter would not fill the CUs (round 6; same results either way:
-                // kernels_lafuse.h).  DDIF_LA_NW = 8 / 4 forces one form (tests/test_env_switches.py).
-                int la_nw = 8;
-                if (!la8) {
-                    static const int nw_env = [] { const char* e = getenv("DDIF_LA_NW"); return e ? atoi(e) : 0; }();
-                    const long wg8 = (long)B * ((Wl + lafuse_strip(Hl, 8) - 1) / lafuse_strip(Hl, 8));
-                    la_nw = nw_env == 4 || nw_env == 8 ? nw_env : (wg8 < num_cus() ? 4 : 8);
-                }
-                if (!dry) DDIF_TRY(la8 ? lafuse8_launch(a, 1, nullptr, true) : lafuse_launch(a, 1, nullptr, true, la_nw));
-                const int nstrips = la8 ? 2 : (Wl + lafuse_strip(Hl, la_nw) - 1) / lafuse_strip(Hl, la_nw);
-                long cap = num_cus();
-                if (g_debug_grid_cap > 0 && g_debug_grid_cap < cap) cap = g_debug_grid_cap;
-                Op op;
-                op.name = "linattn_fused";
-                {
-                    char lb[160];
-                    snprintf(lb, sizeof lb, "linattn_fused GN+dw3x3+q.1+softmax_H+attn_out+res %d+%d->%d @%dx%d", cur.C, skip.C, pm->cout, Hl, Wl);
-                    op.label = lb;
-                }
-                op.flop = 2.0 * B * Hl * Wl * ((double)fea * fea + 9.0 * fea + 2.0 * fea * pm->cout);
-                op.bytes = 4.0 * B * Hl * Wl * ((double)fea + pm->cout);
-                op.cls = (Hl * Wl <= 256) ? 2 : 1;
-                // q.1 on f16x2 (x3), attn_out / attn_res on bf16x3 (x6): weight of the sum
-                op.mfma_w = (3.0 * fea * fea + 6.0 * 2.0 * fea * pm->cout) / ((double)fea * fea + 9.0 * fea + 2.0 * fea * pm->cout);
-                if (la8) op.name = "linattn8_fused";
-                op.run = [a, nstrips, cap, la8, la_nw](hipStream_t st, const StepCtx&) {
-                    const long nw = (long)a.B * nstrips;
-                    if (la8) (void)lafuse8_launch(a, (int)(nw < cap ? nw : cap), st, false);
-                    else (void)lafuse_launch(a, (int)(nw < cap ? nw : cap), st, false, la_nw);
-                };
-                step.push_back(std::move(op));
-                fused_attn = true;
-            }
-        }
-        if (!fused_attn) {
-        DDIF_TRY(alloc_tensor(&xn, fea, Hl, Wl, true));
-        if (pq1->ck != 32 || cur.C % 4 != 0 || skip.C % 4 != 0 || fea > 256)
-            return fail(DDIF_ERR_INVALID, "%s: the fused q = 1x1(dw3x3(GN(cat))) kernel needs 4 | channels and <= 256 of them (got %d+%d)", ci.c_str(), cur.C, skip.C);
-        float *qmx = nullptr, *qsm = nullptr;
-        if (pick_cfg(1, 32, PRO_NONE, 1, 1, 0, Hl, Wl, pq1->cout, B, fea, fea) >= 20) {
-            // low-resolution levels: xn = GN(cat), dwq = depthwise3x3(xn) from ONE small kernel (whole sample per workgroup),
-            // then q = q.1(dwq) on the split-K kernel -- fused into the 1x1 conv the depthwise pass would be recomputed by
-            // every 32-cout tile (sr3_dwt.py:507-513,537,540)
-            Tensor dwq;
-            DDIF_TRY(alloc_tensor(&dwq, fea, Hl, Wl, true));
-            use(cur.p);
-            use(skip.p);
-            use(xn.p);
             DwArgs a{};
-            a.in0 = cur.p;
-            a.c0 = cur.C;
-            a.in1 = skip.p;
-            a.c1 = skip.C;
+            a.in0 = p.cdec[lev].p;
+            a.c0 = cd;
             a.B = B;
             a.H = Hl;
             a.W = Wl;
-            a.st0 = cur.st;
-            a.np0 = cur.np;
-            a.st1 = skip.st;
-            a.np1 = skip.np;
-            a.gamma = pn_g;
-            a.beta = pn_b;
-            a.w = q0w;
-            a.out_dw = dwq.p;
-            a.out_xn = xn.p;
-            a.use_gn = 1;
+            a.w = V(D.ci + ".kv.0.weight");
+            if (!a.w) return fail(DDIF_ERR_MISSING, "%s.kv.0.weight missing", D.ci.c_str());
+            a.out_dw = D.kdw.p;
+            a.tiles_x = (Wl + 15) / 16;
+            a.tiles_y = (Hl + 7) / 8;
             Op op;
-            op.name = "q.gn_dw3x3";
-            op.cls = 2;
-            {
-                char lb[160];
-                snprintf(lb, sizeof lb, "q.gn_dw3x3 %d+%d @%dx%d", cur.C, skip.C, Hl, Wl);
-                op.label = lb;
-            }
+            op.name = "kv.dw3x3";
+            op.flop = 2.0 * 9 * B * Hl * Wl * cd;
+            op.bytes = 8.0 * B * Hl * Wl * cd;
+            op.run = [a](hipStream_t s, const StepCtx&) { launch_dw3x3(s, a); };
+            pre.push_back(std::move(op));
+        }
+        ConvSpec s;
+        DDIF_TRY(need_conv(D.ci + ".kv.1", &s.pc));
+        s.in0 = D.kdw;
+        s.name = "kv.1x1";
+        DDIF_TRY(p.add_conv(pre, s, &D.kv));
+        if (train) return 0;  // (the train-mode forward runs the attention core itself)
+        float *kmx = nullptr, *ksm = nullptr, *ctx = nullptr;
+        DDIF_TRY(p.dalloc(&kmx, (size_t)B * Hl * fea));
+        DDIF_TRY(p.dalloc(&ksm, (size_t)B * Hl * fea));
+        DDIF_TRY(p.dalloc(&ctx, (size_t)B * 8 * d * d));
+        D.ctx = ctx;
+        const Tensor kv = D.kv;
+        {
+            Op op;
+            op.name = "k.softmax_stats";
+            op.bytes = 8.0 * B * Hl * Wl * fea;
+            op.run = [kv, kmx, ksm, fea, BB, Hl, Wl](hipStream_t s, const StepCtx&) {
+                hipLaunchKernelGGL(softmax_stats_kernel, ew_grid((size_t)BB * Hl * fea), dim3(256), 0, s, (const float*)kv.p, 2 * fea, 0, fea, BB, Hl, Wl, 1, kmx, ksm);
+            };
+            pre.push_back(std::move(op));
+        }
+        {
+            Op op;
+            op.name = "linattn_ctx";
+            op.flop = 2.0 * B * 8 * d * d * (double)Hl * Wl;
+            op.bytes = 4.0 * B * Hl * Wl * 2.0 * fea;
+            op.run = [kv, kmx, ksm, ctx, fea, d, BB, Hl, Wl](hipStream_t s, const StepCtx&) {
+                hipLaunchKernelGGL(linattn_ctx_kernel, dim3(8, BB), dim3(256), 2 * 32 * d * sizeof(float), s, (const float*)kv.p, (const float*)kmx, (const float*)ksm, BB, Hl, Wl, fea, d, ctx);
+            };
+            pre.push_back(std::move(op));
+        }
+        return 0;
+    }
+    // xn = GN(cat[h, skip]), dwq = dw3x3(xn): the two-source arguments of dw3x3_kernel / gn_dw3x3_small_kernel (the caller adds its tiling / partition)
+    DwArgs gn_dw_args(const Dec& D, Tensor dwq, Tensor xn) const {
+        DwArgs a{};
+        a.in0 = cur.p;
+        a.c0 = cur.C;
+        a.in1 = D.skip.p;
+        a.c1 = D.skip.C;
+        a.B = B;
+        a.H = D.Hl;
+        a.W = D.Wl;
+        a.st0 = cur.st;
+        a.np0 = cur.np;
+        a.st1 = D.skip.st;
+        a.np1 = D.skip.np;
+        a.gamma = D.pn_g;
+        a.beta = D.pn_b;
+        a.w = D.q0w;
+        a.out_dw = dwq.p;
+        a.out_xn = xn.p;
+        a.use_gn = 1;
+        return a;
+    }
+    // cond-only: M_b = scale * W_out . blockdiag(ctx_b^T), packed per sample next to W_res (null: attn_res is Identity) -- as bf16x3 planes (x3) or fp32 fragments
+    void pack_mix_weights(const Dec& D, const float* wo, const float* wr, float* wmix, int co_n, int ck, int nch, int nb_pad, size_t per, bool x3) {
+        Op op;
+        op.name = "pack_mix_weights";
+        const float scale = 1.0f / std::sqrt((float)D.d);
+        const int BB = B, fea = D.fea, d = D.d;
+        const float* ctx = D.ctx;
+        op.flop = 2.0 * B * co_n * (double)fea * d;
+        op.run = [wo, wr, ctx, wmix, BB, co_n, fea, d, scale, ck, nch, nb_pad, per, x3](hipStream_t s, const StepCtx&) {
+            if (x3) hipLaunchKernelGGL(pack_mix_weights_x3_kernel, ew_grid(per * BB), dim3(256), 0, s, wo, wr, (const float*)ctx, BB, co_n, fea, d, scale, ck, nch, nb_pad, wmix);
+            else hipLaunchKernelGGL(pack_mix_weights_kernel, ew_grid(per * BB), dim3(256), 0, s, wo, wr, (const float*)ctx, BB, co_n, fea, d, scale, ck, nch, nb_pad, wmix);
+        };
+        pre.push_back(std::move(op));
+    }
+    // train: f0 = ffn.0(a); f1 = silu(f0); f2 = ffn.2(f1); f3c = ffn.3(f2) + b   (every intermediate kept for the reverse pass)
+    int ffn_train(const Dec& D, Tensor a, Tensor* f0, Tensor* f1, Tensor* f2, Tensor* f3c) {
+        const int Hl = D.Hl, Wl = D.Wl;
+        ConvSpec s;
+        DDIF_TRY(need_conv(D.ci + ".ffn.0", &s.pc));
+        s.in0 = a;
+        s.use_bias = false;
+        s.name = "ffn.0 (train)";
+        DDIF_TRY(p.add_conv(step, s, f0));
+        DDIF_TRY(p.alloc_tensor(f1, f0->C, f0->H, f0->W, true));
+        Op op;
+        op.name = "silu";
+        op.cls = cls_small(Hl * Wl, 5);
+        op.bytes = 8.0 * B * Hl * Wl * f0->C;
+        Tensor ff0 = *f0, ff1 = *f1;
+        const size_t n = (size_t)B * Hl * Wl * f0->C;
+        op.run = [ff0, ff1, n](hipStream_t st, const StepCtx&) { tk::silu_fwd(st, ff0.p, n, ff1.p); };
+        step.push_back(std::move(op));
+        ConvSpec s2;
+        DDIF_TRY(need_conv(D.ci + ".ffn.2", &s2.pc));
+        s2.in0 = *f1;
+        s2.use_bias = false;
+        s2.name = "ffn.2 (train)";
+        DDIF_TRY(p.add_conv(step, s2, f2));
+        ConvSpec s3;
+        DDIF_TRY(need_conv(D.ci + ".ffn.3", &s3.pc));
+        s3.in0 = *f2;
+        s3.name = "ffn.3 (train)";
+        return p.add_conv(step, s3, f3c);
+    }
+    // train: out = a + ffn_drop_path(f3c)  (sr3_dwt.py:576): the per-sample DropPath scale sits between the conv and the residual
+    int droppath_add(Tensor f3c, Tensor a, Tensor* out, float** scale_out) {
+        Tensor f3;
+        float* scale = nullptr;
+        DDIF_TRY(p.alloc_tensor(&f3, f3c.C, f3c.H, f3c.W, true));
+        DDIF_TRY(p.dalloc(&scale, (size_t)B));
+        p.path_sites.push_back(scale);
+        const int HW = f3c.H * f3c.W, Cc = f3c.C, BB = B;
+        int chunks = (HW * Cc / 4 + 256 * 8 - 1) / (256 * 8);
+        if (chunks < 1) chunks = 1;
+        f3.np = chunks;
+        DDIF_TRY(p.dalloc(&f3.st, (size_t)B * chunks * 2));
+        Op op;
+        op.name = "droppath_add";
+        op.cls = cls_small(HW, 5);
+        op.bytes = 12.0 * B * HW * Cc;
+        op.run = [f3c, scale, a, f3, HW, Cc, BB, chunks](hipStream_t s, const StepCtx&) {
+            hipLaunchKernelGGL(droppath_add_kernel, dim3(chunks, BB), dim3(256), 64, s, (const float*)f3c.p, (const float*)scale, (const float*)a.p, HW, Cc, f3.p, f3.st);
+        };
+        step.push_back(std::move(op));
+        *out = f3;
+        *scale_out = scale;
+        return 0;
+    }
+    // ---- train mode: the block op by op (models/sr3_dwt.py:536-577), every intermediate the reverse pass needs kept in memory:
+    //   xn = GN(cat[h, skip]), dwq = dw3x3(xn)        one launch (dw3x3_kernel, two sources, GroupNorm from the producers' partials)
+    //   q = q.1(dwq);  o = linear attention(q, kv)     (kv comes from set_cond);  a = attn_out(o) + attn_res(xn)  as one 1x1 conv over cat[o, xn]
+    //   f0 = ffn.0(a); f1 = silu(f0); f2 = ffn.2(f1); f3c = ffn.3(f2) + b;  out = a + DropPath(f3c)
+    int decoder_block_train(const Dec& D, Tensor* out) {
+        const std::string& ci = D.ci;
+        const int BB = B, fea = D.fea, d = D.d, Hl = D.Hl, Wl = D.Wl;
+        const PackedConv* pq1t = PC(ci + ".q.1");
+        const PackedConv* pmixt = PC(ci + ".attn_mix");
+        if (!pq1t || !pmixt) return fail(DDIF_ERR_MISSING, "%s: q.1 / attn_out missing", ci.c_str());
+        if (!cur.st || !D.skip.st) return fail(DDIF_ERR_STATE, "%s: prenorm without producer statistics", ci.c_str());
+        if (!D.pn_g || !D.pn_b || !D.q0w) return fail(DDIF_ERR_MISSING, "%s: prenorm/q.0 weights missing", ci.c_str());
+        Tensor xn, dwq, q, o, a, f0, f1, f2, f3c, f3, kdw_pad;
+        float *la_ctx = nullptr, *la_part = nullptr;
+        DDIF_TRY(p.alloc_tensor(&xn, fea, Hl, Wl, true));
+        DDIF_TRY(p.alloc_tensor(&dwq, fea, Hl, Wl, true));
+        {
+            DwArgs da = gn_dw_args(D, dwq, xn);
+            da.tiles_x = (Wl + 15) / 16;
+            da.tiles_y = (Hl + 7) / 8;
+            Op op;
+            op.name = "q.gn_dw3x3 (train)";
+            op.cls = cls_small(Hl * Wl, 5);
             op.flop = 2.0 * 9 * B * Hl * Wl * fea;
-            op.bytes = 4.0 * B * Hl * Wl * 3.0 * fea;
-            const size_t sm = (size_t)(Hl + 2) * (Wl + 2) * 36 * sizeof(float);
-            if (sm > 64 * 1024) DDIF_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(gn_dw3x3_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-            a.xcd = (xcd_mask() & 8) ? 1 : 0;
-            const dim3 gdw = a.xcd ? dim3(BB, (fea + 31) / 32) : dim3((fea + 31) / 32, BB);
-            op.run = [a, gdw, sm](hipStream_t s, const StepCtx&) { hipLaunchKernelGGL(gn_dw3x3_small_kernel, gdw, dim3(256), sm, s, a); };
+            op.bytes = 12.0 * B * Hl * Wl * fea;
+            op.run = [da](hipStream_t s, const StepCtx&) { launch_dw3x3(s, da); };
             step.push_back(std::move(op));
+        }
+        {
             ConvSpec s;
-            s.pc = pq1;
+            s.pc = pq1t;
             s.in0 = dwq;
-            s.name = "q.1x1";
-            if (Hl <= 16) {  // whole columns inside one tile: softmax_H statistics of q from the conv's epilogue
-                DDIF_TRY(dalloc(&qmx, (size_t)B * Wl * fea));
-                DDIF_TRY(dalloc(&qsm, (size_t)B * Wl * fea));
-                s.cso_mx = qmx;
-                s.cso_sm = qsm;
-                s.name = "q.1x1 (+softmax_H stats)";
+            s.name = "q.1x1 (train)";
+            DDIF_TRY(p.add_conv(step, s, &q));
+        }
+        DDIF_TRY(p.alloc_tensor(&o, fea, Hl, Wl, true));
+        {
+            Op op;
+            op.name = "linattn_fwd";
+            op.cls = cls_small(Hl * Wl, 5);
+            op.flop = 4.0 * B * 8 * d * d * (double)Hl * Wl;
+            op.bytes = 16.0 * B * Hl * Wl * fea;
+            Tensor qq = q, kk = D.kv, oo = o;
+            if ((Hl > Wl ? Hl : Wl) * fea > 8192 || d > 32 || d % 4)
+                return fail(DDIF_ERR_INVALID, "%s: train-mode linear attention holds one image line x %d channels in LDS: lines of more than %d pixels are not supported",
+                            ci.c_str(), fea, 8192 / fea);
+            DDIF_TRY(p.dalloc(&la_ctx, (size_t)B * fea * d));
+            DDIF_TRY(p.dalloc(&la_part, tk::linattn_part_floats(B, Hl, Wl, fea, d)));
+            float *cx = la_ctx, *pt = la_part;
+            {   // cond-only half: softmax_W(k), context = k v^T per head (sr3_dwt.py:541,546,563) -- part of set_cond, like the eval plan's
+                Op pc;
+                pc.name = "linattn_ctx (train)";
+                pc.bytes = 8.0 * B * Hl * Wl * fea;
+                pc.run = [kk, BB, d, Hl, Wl, cx, pt](hipStream_t s, const StepCtx&) { tk::linattn_ctx(s, kk.p, BB, 8, d, Hl, Wl, cx, pt); };
+                pre.push_back(std::move(pc));
+                for (size_t i = D.pre_dec0; i < pre.size(); ++i) pre[i].side = true;
             }
-            DDIF_TRY(add_conv(step, s, &q));
+            op.run = [qq, oo, BB, d, Hl, Wl, fea, cx](hipStream_t s, const StepCtx&) { tk::linattn_apply(s, qq.p, cx, BB, 8, d, Hl, Wl, oo.p, fea); };
+            step.push_back(std::move(op));
+        }
+        const bool has_res = pmixt->cin == 2 * fea;
+        {
+            ConvSpec s;
+            s.pc = pmixt;
+            s.in0 = o;
+            if (has_res) s.in1 = xn;
+            else s.res = xn.p;  // attn_res is Identity
+            s.name = "attn_out+res (train)";
+            DDIF_TRY(p.add_conv(step, s, &a));
+        }
+        DDIF_TRY(ffn_train(D, a, &f0, &f1, &f2, &f3c));
+        float* scale = nullptr;
+        DDIF_TRY(droppath_add(f3c, a, &f3, &scale));
+        // kv.0's output zero-padded to 4 | channels: input of kv.1's weight gradient (cond-only)
+        DDIF_TRY(p.alloc_tensor(&kdw_pad, (D.cd + 3) & ~3, Hl, Wl));
+        Plan::TrainMod& m = tmod(Plan::TrainMod::DEC, ci, cur, f3);
+        m.t[0] = D.skip;
+        m.t[1] = xn;
+        m.t[2] = dwq;
+        m.t[3] = q;
+        m.t[4] = D.kv;
+        m.t[5] = D.kdw;
+        m.t[6] = kdw_pad;
+        m.t[7] = o;
+        m.t[8] = a;
+        m.t[9] = f0;
+        m.t[10] = f1;
+        m.t[11] = f2;
+        m.scale = scale;
+        m.ctx = la_ctx;
+        m.la_part = la_part;
+        m.has_res = has_res;
+        m.skip_from = D.skip_from;
+        m.lev = lev;
+        // f3c is only needed by the reverse pass through DropPath's scale: d(f3c) = scale * d(out); not stored in the record
+        *out = f3;
+        return 0;
+    }
+    // ---- inference: the whole attention half in ONE launch where the level keeps whole image columns inside a workgroup (kernels_lafuse.h):
+    //      xn = GN(cat[h, skip]) -> q = q.1(q.0(xn)) -> softmax over H -> M_b p + W_res xn + bias; q and xn never reach memory.
+    //      *fused = false: the level / shapes / weights do not admit it, nothing was emitted
+    int linattn_fused(const Dec& D, const PackedConv* pq1, Tensor* amix, bool* fused) {
+        const std::string& ci = D.ci;
+        const int fea = D.fea, Hl = D.Hl, Wl = D.Wl;
+        const Tensor& skip = D.skip;
+        *fused = false;
+        const PackedConv* pm = PC(ci + ".attn_mix");
+        const float* wr = V(ci + ".attn_res.weight");
+        // (round 6) the 8 x 8 level has a kernel of its own: half a sample per workgroup, the waves split the output channels (kernels_lafuse8.h)
+        const bool la8 = la8_enabled() && lafuse8_supported(Hl, Wl, cur.C, skip.C, pm ? pm->cout : 0);
+        bool ok = lafuse_enabled() && f16_enabled() && x3_enabled() && lr_enabled() && pm && wr && pq1->w_f16 && pq1->bias && pm->bias && (Hl * Wl >= 256 || la8) &&
+                  pq1->cout == fea && pq1->ck == 32 && pm->ck == 32 && pm->cin == 2 * fea && cur.C % 16 == 0 && skip.C % 16 == 0 && (la8 || lafuse_supported(Hl, fea, pm->cout));
+        if (ok) {  // f16x2 range of depthwise(GroupNorm(.)): (sqrt(N) max|gamma| + max|beta|) * 9 max|w_dw| inside the scaled half range
+            auto ig = net.vec_absmax.find(D.pn_g), ib = net.vec_absmax.find(D.pn_b), iw = net.vec_absmax.find(D.q0w);
+            ok = ig != net.vec_absmax.end() && ib != net.vec_absmax.end() && iw != net.vec_absmax.end() &&
+                 (std::sqrt((double)fea * Hl * Wl) * ig->second + ib->second) * 9.0 * iw->second < DDIF_F16_AMAX;
+        }
+        if (!ok) return 0;
+        const float* wo = V(ci + ".attn_out.weight");
+        if (!wo) return fail(DDIF_ERR_MISSING, "%s.attn_out.weight missing", ci.c_str());
+        const int nb_pad = (((pm->cout + 31) / 32) + 3) & ~3;
+        const size_t per = (size_t)nb_pad * pm->n_chunks * 2 * 3 * 256;  // bf16x3 planes, 32-channel chunks
+        float* wmix = nullptr;
+        DDIF_TRY(p.dalloc(&wmix, per * B));
+        pack_mix_weights(D, wo, wr, wmix, pm->cout, 32, pm->n_chunks, nb_pad, per, true);
+        p.use(cur.p);
+        p.use(skip.p);
+        DDIF_TRY(p.alloc_tensor(amix, pm->cout, Hl, Wl, true));
+        LaFuseArgs a{};
+        a.xcd = (xcd_mask() & 4) ? 1 : 0;
+        a.in0 = cur.p;
+        a.c0 = cur.C;
+        a.in1 = skip.p;
+        a.c1 = skip.C;
+        a.B = B;
+        a.H = Hl;
+        a.W = Wl;
+        a.st0 = cur.st;
+        a.np0 = cur.np;
+        a.st1 = skip.st;
+        a.np1 = skip.np;
+        a.gamma = D.pn_g;
+        a.beta = D.pn_b;
+        a.dw_w = D.q0w;
+        a.wq = pq1->w_f16;
+        a.nchq = pq1->n_chunks;
+        a.bq = pq1->bias;
+        a.wmix = wmix;
+        a.wmix_bstride = (long long)per;
+        a.nch_mix = pm->n_chunks;
+        a.bias = pm->bias;
+        a.out = amix->p;
+        a.dout = pm->cout;
+        // four-wave workgroups of 128 pixels instead of eight-wave ones of 256 when the latter would not fill the CUs (round 6; same results either way:
+        // kernels_lafuse.h).  DDIF_LA_NW = 8 / 4 forces one form (tests/test_env_switches.py).
+        int la_nw = 8;
+        if (!la8) {
+            static const int nw_env = env_int("DDIF_LA_NW", 0);
+            const long wg8 = (long)B * ((Wl + lafuse_strip(Hl, 8) - 1) / lafuse_strip(Hl, 8));
+            la_nw = nw_env == 4 || nw_env == 8 ? nw_env : (wg8 < num_cus() ? 4 : 8);
+        }
+        if (!p.dry) DDIF_TRY(la8 ? lafuse8_launch(a, 1, nullptr, true) : lafuse_launch(a, 1, nullptr, true, la_nw));
+        const int nstrips = la8 ? 2 : (Wl + lafuse_strip(Hl, la_nw) - 1) / lafuse_strip(Hl, la_nw);
+        long cap = num_cus();
+        if (g_debug_grid_cap > 0 && g_debug_grid_cap < cap) cap = g_debug_grid_cap;
+        Op op;
+        op.name = la8 ? "linattn8_fused" : "linattn_fused";
+        {
+            char lb[160];
+            snprintf(lb, sizeof lb, "linattn_fused GN+dw3x3+q.1+softmax_H+attn_out+res %d+%d->%d @%dx%d", cur.C, skip.C, pm->cout, Hl, Wl);
+            op.label = lb;
+        }
+        op.flop = 2.0 * B * Hl * Wl * ((double)fea * fea + 9.0 * fea + 2.0 * fea * pm->cout);
+        op.bytes = 4.0 * B * Hl * Wl * ((double)fea + pm->cout);
+        op.cls = cls_small(Hl * Wl, 1);
+        // q.1 on f16x2 (x3), attn_out / attn_res on bf16x3 (x6): weight of the sum
+        op.mfma_w = (3.0 * fea * fea + 6.0 * 2.0 * fea * pm->cout) / ((double)fea * fea + 9.0 * fea + 2.0 * fea * pm->cout);
+        op.run = [a, nstrips, cap, la8, la_nw](hipStream_t st, const StepCtx&) {
+            const long nw = (long)a.B * nstrips;
+            if (la8) (void)lafuse8_launch(a, (int)(nw < cap ? nw : cap), st, false);
+            else (void)lafuse_launch(a, (int)(nw < cap ? nw : cap), st, false, la_nw);
+        };
+        step.push_back(std::move(op));
+        *fused = true;
+        return 0;
+    }
+    // low-resolution levels: xn = GN(cat), dwq = depthwise3x3(xn) from ONE small kernel (whole sample per workgroup), then q = q.1(dwq) on the split-K
+    // kernel -- fused into the 1x1 conv the depthwise pass would be recomputed by every 32-cout tile (sr3_dwt.py:507-513,537,540)
+    int q_low_resolution(const Dec& D, const PackedConv* pq1, Tensor xn, Tensor* q, float** qmx, float** qsm) {
+        const int BB = B, fea = D.fea, Hl = D.Hl, Wl = D.Wl;
+        Tensor dwq;
+        DDIF_TRY(p.alloc_tensor(&dwq, fea, Hl, Wl, true));
+        p.use(cur.p);
+        p.use(D.skip.p);
+        p.use(xn.p);
+        DwArgs a = gn_dw_args(D, dwq, xn);
+        Op op;
+        op.name = "q.gn_dw3x3";
+        op.cls = 2;
+        {
+            char lb[160];
+            snprintf(lb, sizeof lb, "q.gn_dw3x3 %d+%d @%dx%d", cur.C, D.skip.C, Hl, Wl);
+            op.label = lb;
+        }
+        op.flop = 2.0 * 9 * B * Hl * Wl * fea;
+        op.bytes = 4.0 * B * Hl * Wl * 3.0 * fea;
+        const size_t sm = (size_t)(Hl + 2) * (Wl + 2) * 36 * sizeof(float);
+        if (sm > 64 * 1024) DDIF_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(gn_dw3x3_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+        a.xcd = (xcd_mask() & 8) ? 1 : 0;
+        const dim3 gdw = a.xcd ? dim3(BB, (fea + 31) / 32) : dim3((fea + 31) / 32, BB);
+        op.run = [a, gdw, sm](hipStream_t s, const StepCtx&) { hipLaunchKernelGGL(gn_dw3x3_small_kernel, gdw, dim3(256), sm, s, a); };
+        step.push_back(std::move(op));
+        ConvSpec s;
+        s.pc = pq1;
+        s.in0 = dwq;
+        s.name = "q.1x1";
+        if (Hl <= 16) {  // whole columns inside one tile: softmax_H statistics of q from the conv's epilogue
+            DDIF_TRY(p.dalloc(qmx, (size_t)B * Wl * fea));
+            DDIF_TRY(p.dalloc(qsm, (size_t)B * Wl * fea));
+            s.cso_mx = *qmx;
+            s.cso_sm = *qsm;
+            s.name = "q.1x1 (+softmax_H stats)";
+        }
+        return p.add_conv(step, s, q);
+    }
+    // inference, where the fused block does not apply: q conv (-> xn, q), column statistics of q, attn_out conv on per-sample weights
+    int linattn_three_launch(const Dec& D, const PackedConv* pq1, Tensor* amix) {
+        const std::string& ci = D.ci;
+        const int BB = B, fea = D.fea, Hl = D.Hl, Wl = D.Wl;
+        const Tensor& skip = D.skip;
+        Tensor xn, q;
+        DDIF_TRY(p.alloc_tensor(&xn, fea, Hl, Wl, true));
+        if (pq1->ck != 32 || cur.C % 4 != 0 || skip.C % 4 != 0 || fea > 256)
+            return fail(DDIF_ERR_INVALID, "%s: the fused q = 1x1(dw3x3(GN(cat))) kernel needs 4 | channels and <= 256 of them (got %d+%d)", ci.c_str(), cur.C, skip.C);
+        float *qmx = nullptr, *qsm = nullptr;
+        if (pick_cfg(CfgQuery{1, 32, PRO_NONE, 1, 1, 0, Hl, Wl, pq1->cout, B, fea, fea}) >= 20) {
+            DDIF_TRY(q_low_resolution(D, pq1, xn, &q, &qmx, &qsm));
         } else {
             // q = q.1(depthwise3x3(GroupNorm(cat[h, skip]))) in ONE kernel; also emits xn (sr3_dwt.py:507-513,537,540)
             ConvSpec s;
@@ -1462,17 +1431,17 @@ int Plan::build_impl() {
             s.in0 = cur;
             s.in1 = skip;
             s.pro = PRO_GN_DW;
-            s.gamma = pn_g;
-            s.beta = pn_b;
-            s.dw_w = q0w;
+            s.gamma = D.pn_g;
+            s.beta = D.pn_b;
+            s.dw_w = D.q0w;
             s.out_xn = xn.p;
             s.name = "q = 1x1(dw3x3(GN(cat)))";
-            DDIF_TRY(add_conv(step, s, &q));
+            DDIF_TRY(p.add_conv(step, s, &q));
         }
         if (!qmx) {
-            DDIF_TRY(dalloc(&qmx, (size_t)B * Wl * fea));
-            DDIF_TRY(dalloc(&qsm, (size_t)B * Wl * fea));
-            use(q.p);
+            DDIF_TRY(p.dalloc(&qmx, (size_t)B * Wl * fea));
+            DDIF_TRY(p.dalloc(&qsm, (size_t)B * Wl * fea));
+            p.use(q.p);
             Op op;
             op.name = "q.softmax_stats";
             op.cls = 4;
@@ -1486,141 +1455,156 @@ int Plan::build_impl() {
         if (!pmix) return fail(DDIF_ERR_MISSING, "%s.attn_out missing", ci.c_str());
         // the linear-attention context is folded into per-sample attn_out weights (needs 32-channel chunks)
         if (fea % 32 != 0 || pmix->ck != 32) return fail(DDIF_ERR_INVALID, "%s: linear attention over %d channels needs 32 | channels", ci.c_str(), fea);
-        {
-            // cond-only: M_b = scale * W_out . blockdiag(ctx_b^T), packed per sample next to W_res
-            const int nb_pad = (((pmix->cout + 31) / 32) + 3) & ~3;
-            // the layout follows the instantiation add_conv() will pick for this conv (bf16x3 planes or fp32 fragments)
-            const bool mix_x3 = pick_cfg(1, pmix->ck, PRO_COLSM, 1, 1, 0, Hl, Wl, pmix->cout, B, pmix->cin, pmix->cin == 2 * fea ? fea : pmix->cin) >= 12;
-            const size_t per = mix_x3 ? (size_t)nb_pad * pmix->n_chunks * (pmix->ck / 16) * 3 * 256 : (size_t)nb_pad * pmix->n_chunks * (pmix->ck / 8) * 256;
-            float* wmix = nullptr;
-            DDIF_TRY(dalloc(&wmix, per * B));
-            const float* wo = V(ci + ".attn_out.weight");
-            const float* wr = V(ci + ".attn_res.weight");  // null: attn_res is Identity
-            if (!wo) return fail(DDIF_ERR_MISSING, "%s.attn_out.weight missing", ci.c_str());
-            {
-                Op op;
-                op.name = "pack_mix_weights";
-                const float scale = 1.0f / std::sqrt((float)d);
-                const int co_n = pmix->cout, ck = pmix->ck, nch = pmix->n_chunks;
-                op.flop = 2.0 * B * co_n * (double)fea * d;
-                op.run = [wo, wr, ctx, wmix, BB, co_n, fea, d, scale, ck, nch, nb_pad, per, mix_x3](hipStream_t s, const StepCtx&) {
-                    if (mix_x3)
-                        hipLaunchKernelGGL(pack_mix_weights_x3_kernel, ew_grid(per * BB), dim3(256), 0, s, wo, wr, (const float*)ctx, BB, co_n, fea, d, scale, ck, nch, nb_pad, wmix);
-                    else
-                        hipLaunchKernelGGL(pack_mix_weights_kernel, ew_grid(per * BB), dim3(256), 0, s, wo, wr, (const float*)ctx, BB, co_n, fea, d, scale, ck, nch, nb_pad, wmix);
-                };
-                pre.push_back(std::move(op));
-            }
-            ConvSpec s;
-            s.pc = pmix;
-            s.in0 = q;
-            if (pmix->cin == 2 * fea) s.in1 = xn;
-            else s.res = xn.p;  // attn_res is Identity
-            s.pro = PRO_COLSM;
-            s.cs_mx = qmx;
-            s.cs_sm = qsm;
-            s.w_override = wmix;
-            s.w_bstride = (long long)per;
-            s.name = "softmax_H(q).ctx.attn_out+res";
-            DDIF_TRY(add_conv(step, s, &amix));
+        const int nb_pad = (((pmix->cout + 31) / 32) + 3) & ~3;
+        // the layout follows the instantiation add_conv() will pick for this conv (bf16x3 planes or fp32 fragments)
+        const bool mix_x3 = pick_cfg(CfgQuery{1, pmix->ck, PRO_COLSM, 1, 1, 0, Hl, Wl, pmix->cout, B, pmix->cin, pmix->cin == 2 * fea ? fea : pmix->cin}) >= 12;
+        const size_t per = mix_x3 ? (size_t)nb_pad * pmix->n_chunks * (pmix->ck / 16) * 3 * 256 : (size_t)nb_pad * pmix->n_chunks * (pmix->ck / 8) * 256;
+        float* wmix = nullptr;
+        DDIF_TRY(p.dalloc(&wmix, per * B));
+        const float* wo = V(ci + ".attn_out.weight");
+        const float* wr = V(ci + ".attn_res.weight");  // null: attn_res is Identity
+        if (!wo) return fail(DDIF_ERR_MISSING, "%s.attn_out.weight missing", ci.c_str());
+        pack_mix_weights(D, wo, wr, wmix, pmix->cout, pmix->ck, pmix->n_chunks, nb_pad, per, mix_x3);
+        ConvSpec s;
+        s.pc = pmix;
+        s.in0 = q;
+        if (pmix->cin == 2 * fea) s.in1 = xn;
+        else s.res = xn.p;  // attn_res is Identity
+        s.pro = PRO_COLSM;
+        s.cs_mx = qmx;
+        s.cs_sm = qsm;
+        s.w_override = wmix;
+        s.w_bstride = (long long)per;
+        s.name = "softmax_H(q).ctx.attn_out+res";
+        return p.add_conv(step, s, amix);
+    }
+    // inference: f1 = silu(ffn.0(a)), then ffn[3] o ffn[2] as ONE 3x3 conv where the net carries the merged weights ".ffn.23" (no nonlinearity between
+    // them; ddif_net.cpp), else as two convs; the residual a rides in the last conv's epilogue.  (The train-mode decoder has its own: ffn_train.)
+    int ffn(const Dec& D, Tensor amix, Tensor* f3) {
+        Tensor f1, f2;
+        ConvSpec s;
+        DDIF_TRY(need_conv(D.ci + ".ffn.0", &s.pc));
+        s.in0 = amix;
+        s.use_bias = false;
+        s.silu = true;
+        s.name = "ffn.0";
+        DDIF_TRY(p.add_conv(step, s, &f1));
+        ConvSpec s2;
+        DDIF_TRY(need_conv(D.ci + ".ffn.2", &s2.pc));
+        s2.in0 = f1;
+        s2.use_bias = false;
+        s2.name = "ffn.2";
+        ConvSpec s3;
+        DDIF_TRY(need_conv(D.ci + ".ffn.3", &s3.pc));
+        if (const PackedConv* pm = PC(D.ci + ".ffn.23")) {
+            ConvSpec sf = s2;
+            sf.pc = pm;
+            sf.use_bias = true;
+            sf.res = amix.p;
+            sf.stats = true;
+            sf.name = "ffn.3(ffn.2) merged + res";
+            return p.add_conv(step, sf, f3);
         }
-        }  // !fused_attn
-        {
-            ConvSpec s;
-            s.pc = PC(ci + ".ffn.0");
-            if (!s.pc) return fail(DDIF_ERR_MISSING, "%s.ffn.0 missing", ci.c_str());
-            s.in0 = amix;
-            s.use_bias = false;
-            s.silu = true;
-            s.name = "ffn.0";
-            DDIF_TRY(add_conv(step, s, &f1));
-            ConvSpec s2;
-            s2.pc = PC(ci + ".ffn.2");
-            if (!s2.pc) return fail(DDIF_ERR_MISSING, "%s.ffn.2 missing", ci.c_str());
-            s2.in0 = f1;
-            s2.use_bias = false;
-            s2.name = "ffn.2";
-            ConvSpec s3;
-            s3.pc = PC(ci + ".ffn.3");
-            if (!s3.pc) return fail(DDIF_ERR_MISSING, "%s.ffn.3 missing", ci.c_str());
-            // eval: ffn[3] o ffn[2] is one 3x3 conv (no nonlinearity between them; merged weights ".ffn.23", ddif_net.cpp)
-            bool fused_ffn3 = false;
-            if (const PackedConv* pm = train_mode ? nullptr : PC(ci + ".ffn.23")) {
-                ConvSpec sf = s2;
-                sf.pc = pm;
-                sf.use_bias = true;
-                sf.res = amix.p;
-                sf.stats = true;
-                sf.name = "ffn.3(ffn.2) merged + res";
-                DDIF_TRY(add_conv(step, sf, &f3));
-                fused_ffn3 = true;
-            }
-            if (!fused_ffn3) DDIF_TRY(add_conv(step, s2, &f2));
-            s3.in0 = f2;
-            if (fused_ffn3) {
-            } else if (train_mode) {
-                // ffn_drop_path(ffn(a)) + a  (sr3_dwt.py:576): the per-sample DropPath scale sits between the conv and the residual
-                Tensor f3c;
-                s3.name = "ffn.3 (train)";
-                DDIF_TRY(add_conv(step, s3, &f3c));
-                DDIF_TRY(alloc_tensor(&f3, f3c.C, f3c.H, f3c.W, true));
-                use(f3c.p);
-                use(amix.p);
-                float* scale = nullptr;
-                DDIF_TRY(dalloc(&scale, (size_t)B));
-                path_sites.push_back(scale);
-                const int HW = f3c.H * f3c.W, Cc = f3c.C;
-                int chunks = (HW * Cc / 4 + 256 * 8 - 1) / (256 * 8);
-                if (chunks < 1) chunks = 1;
-                f3.np = chunks;
-                DDIF_TRY(dalloc(&f3.st, (size_t)B * chunks * 2));
-                Tensor fo = f3;
-                Op op;
-                op.name = "droppath_add";
-                op.cls = (HW <= 256) ? 2 : 5;
-                op.bytes = 12.0 * B * HW * Cc;
-                op.run = [f3c, scale, amix, fo, HW, Cc, BB, chunks](hipStream_t s, const StepCtx&) {
-                    hipLaunchKernelGGL(droppath_add_kernel, dim3(chunks, BB), dim3(256), 64, s, (const float*)f3c.p, (const float*)scale, (const float*)amix.p, HW, Cc, fo.p, fo.st);
-                };
-                step.push_back(std::move(op));
-            } else {
-                s3.res = amix.p;
-                s3.stats = true;
-                s3.name = "ffn.3";
-                DDIF_TRY(add_conv(step, s3, &f3));
-            }
+        DDIF_TRY(p.add_conv(step, s2, &f2));
+        s3.in0 = f2;
+        s3.res = amix.p;
+        s3.stats = true;
+        s3.name = "ffn.3";
+        return p.add_conv(step, s3, f3);
+    }
+    // FastAttnCondInjection (sr3_dwt.py:495-577) + ResnetBlocWithAttn
+    int decoder_block(const Layer& L) {
+        Dec D;
+        D.ci = L.p + ".cond_inj";
+        D.skip = feats.back();
+        feats.pop_back();
+        if (train) {
+            D.skip_from = feat_mod.back();
+            feat_mod.pop_back();
+        }
+        if (D.skip.C != L.cskip || cur.C != L.cx || D.skip.H != cur.H || D.skip.W != cur.W)
+            return fail(DDIF_ERR_INVALID, "%s: skip/feature shape mismatch", L.p.c_str());
+        D.fea = L.cin;
+        D.d = D.fea / 8;
+        D.Hl = cur.H;
+        D.Wl = cur.W;
+        D.cd = Cl + 3 * Pn;
+        DDIF_TRY(decoder_context(D));
+        const std::string& ci = D.ci;
+        D.pn_g = V(ci + ".prenorm_x.weight");
+        D.pn_b = V(ci + ".prenorm_x.bias");
+        D.q0w = V(ci + ".q.0.weight");
+        Tensor f3;
+        if (train) {
+            DDIF_TRY(decoder_block_train(D, &f3));
+        } else {
+            // ---- per step
+            const PackedConv* pq1 = PC(ci + ".q.1");
+            if (!pq1) return fail(DDIF_ERR_MISSING, "%s.q.1 missing", ci.c_str());
+            if (!cur.st || !D.skip.st) return fail(DDIF_ERR_STATE, "%s: prenorm without producer statistics", ci.c_str());
+            if (!D.pn_g || !D.pn_b || !D.q0w) return fail(DDIF_ERR_MISSING, "%s: prenorm/q.0 weights missing", ci.c_str());
+            Tensor amix;
+            bool fused_attn = false;
+            DDIF_TRY(linattn_fused(D, pq1, &amix, &fused_attn));
+            if (!fused_attn) DDIF_TRY(linattn_three_launch(D, pq1, &amix));
+            DDIF_TRY(ffn(D, amix, &f3));
         }
         DDIF_TRY(resblock(L.p + ".res_block", f3, &cur));
-        if (L.attn) {
-            Tensor t2;
-            DDIF_TRY(attention(L.p + ".attn", cur, &t2));
-            cur = t2;
-        }
+        return attention_if(L);
     }
-    {
+    int final_conv() {
         ConvSpec s;
-        s.pc = PC("final_conv.block.3");
-        if (!s.pc) return fail(DDIF_ERR_MISSING, "final_conv.block.3 missing");
+        DDIF_TRY(need_conv("final_conv.block.3", &s.pc));
         s.in0 = cur;
         s.pro = PRO_GN_SILU;
         s.gamma = V("final_conv.block.0.weight");
         s.beta = V("final_conv.block.0.bias");
         s.name = "final";
         s.samp = true;
-        DDIF_TRY(add_conv(step, s, &net_out));
+        DDIF_TRY(p.add_conv(step, s, &p.net_out));
+        if (train) tmod(Plan::TrainMod::FINAL, "final_conv", cur, p.net_out);
+        return 0;
+    }
+};
+}  // namespace
+
+// UNetSR3.forward (reference models/sr3_dwt.py:169-219) as a launch program, the cond-only branches hoisted into set_cond
+int Plan::build_impl() {
+    const ddif_net_cfg& c = net->cfg;
+    if (!net->committed) return fail(DDIF_ERR_STATE, "ddif_plan_create: ddif_net_commit has not been called");
+    C = c.out_channel;
+    P = c.pan_channel;
+    CC = 2 * c.lms_channel + 4 * P;
+    const int nlev = c.n_channel_mults;
+    const int div = 1 << (nlev - 1);
+    if (B < 1 || H < div || W < div || H % div || W % div)
+        return fail(DDIF_ERR_INVALID, "ddif_plan_create: H=%d W=%d must be positive multiples of %d", H, W, div);
+    LH.assign(1, H);
+    LW.assign(1, W);
+    for (int l = 1; l < nlev; ++l) {
+        LH.push_back((LH.back() - 1) / 2 + 1);
+        LW.push_back((LW.back() - 1) / 2 + 1);
+    }
+    PlanBuilder b(*this);
+    DDIF_TRY(b.boundary_buffers());
+    DDIF_TRY(b.cond_program());
+    for (size_t li = 0; li < net->downs.size(); ++li) {
+        const Layer& L = net->downs[li];
+        DDIF_TRY(L.kind == L_STEM ? b.stem(li) : (L.kind == L_DOWN ? b.down(li) : b.encoder_block(li)));
+        b.feats.push_back(b.cur);
         if (train_mode) {
-            TrainMod m;
-            m.kind = TrainMod::FINAL;
-            m.key = "final_conv";
-            m.in = cur;
-            m.out = net_out;
-            tmods.push_back(m);
+            tmods.back().pushes_feat = true;
+            b.feat_mod.push_back((int)tmods.size() - 1);
         }
     }
+    for (const Layer& L : net->mid) DDIF_TRY(b.mid_block(L));
+    if (train_mode) b.join_side_stream();
+    for (const Layer& L : net->ups) DDIF_TRY(L.kind == L_UP ? b.up(L) : b.decoder_block(L));
+    DDIF_TRY(b.final_conv());
     DDIF_TRY(ensure_tb(B));
     return 0;
-#undef DDIF_TRY
 }
+#undef DDIF_TRY
 
 void Plan::drop_graphs() {
 #ifndef DDIF_EMU
@@ -1640,14 +1624,7 @@ int Plan::ensure_tb(int rows) {
     return 0;
 }
 
-int Plan::time_rows(const float* t_host, int rows, hipStream_t s) {
-    if (int e = ensure_tb(rows)) return e;
-    DDIF_HIPCHK(hipMemcpyAsync(tvals, t_host, (size_t)rows * sizeof(float), hipMemcpyDefault, s));  // host or device source
-    const int inner = net->cfg.inner_channel;
-    hipLaunchKernelGGL(time_embed_kernel, dim3(rows), dim3(128), (size_t)6 * inner * sizeof(float), s, (const float*)tvals,
-                       net->freqs, net->w1, net->b1, net->w3, net->b3, net->wall, net->ball, inner, net->nslots, tb, (float*)nullptr);
-    return 0;
-}
+int Plan::time_rows(const float* t_host, int rows, hipStream_t s) { return time_rows_aux(t_host, rows, nullptr, s); }
 
 static int check_sampler_net(const Net* n);
 
@@ -1971,7 +1948,7 @@ int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int 
     bool graph_ok = false;
     (void)graph_ok;
 #ifndef DDIF_EMU
-    static const bool graph_env = [] { const char* e = getenv("DDIF_GRAPH"); return !e || atoi(e) != 0; }();
+    static const bool graph_env = env_flag("DDIF_GRAPH", true);
     if (use_graph && graph_env && n_steps >= 4) {
         if (!graph_exec[kind]) {
             if (!cap_stream) DDIF_HIPCHK(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));

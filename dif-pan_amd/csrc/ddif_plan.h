@@ -1,10 +1,17 @@
 // Plan: per-(B,H,W) workspaces, the cond-only caches and the launch program of one denoising step.
 #pragma once
+#include <cstdlib>
 #include <string>
 #include <memory>
 #include "ddif_net.h"
 
 namespace ddif {
+
+// Environment switches (DDIF_*): the value of `name` through atoi, `dflt` when it is unset.  Most are read once per process (a function-local static at the
+// point of definition, next to the comment that says what the switch does and which test covers it).
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline bool env_flag(const char* name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; }
+bool train_x3();  // DDIF_TRAIN_X3 (ddif_bwd.cpp)
 
 struct ConvArgs;
 
@@ -115,7 +122,7 @@ void dw3x3_plain(hipStream_t s, const float* in, int C, int B, int H, int W, con
 struct AttnBlockArgs;
 int attn_block_prepare();                                                        // ddif_lr.cpp (kernels_attn.h)
 void attn_block_launch(const AttnBlockArgs& a, int grid, hipStream_t s);
-int attn_block_split();  // workgroups per sample (2 since round 6; DDIF_ATTN_SPLIT=1: one)
+int attn_block_split();  // workgroups per sample (4 since round 6; DDIF_ATTN_SPLIT=1 / 2: one / two)
 
 // round 6: ask add_conv() to fold the NEXT block's CondInjection (x_conv + FiLM) into this conv's epilogue (kernels_conv.h EPI_XF); `done` and `out` come back
 struct XfReq {
@@ -259,7 +266,7 @@ struct Plan {
         int skip_from = -1;          // DEC: index (in tmods) of the module whose output is this block's skip input
     };
     std::vector<TrainMod> tmods;
-    std::vector<Tensor> cenc_pad, kdw_pad_unused;  // train: cond images zero-padded to 4 | channels (weight gradients)
+    std::vector<Tensor> cenc_pad;  // train: cond images zero-padded to 4 | channels (weight gradients)
     std::map<std::string, float*> grad_slots;      // state-dict key -> bound gradient tensor (reference layout), ddif_plan_train_bind
     std::vector<std::function<void(hipStream_t)>> bwd;  // reverse program, in FORWARD order (run back to front)
     struct TrainScratch;

@@ -21,10 +21,6 @@
 
 namespace ddif {
 
-static bool train_x3_() {  // DDIF_TRAIN_X3=0: exact-fp32 MFMA for the dgrad convs (as ddif_bwd.cpp)
-    static const bool v = [] { const char* e = getenv("DDIF_TRAIN_X3"); return !e || atoi(e) != 0; }();
-    return v;
-}
 static inline void dd_wait_event(hipStream_t s, hipEvent_t e) {  // (the host emulator runs everything in order on one stream: never reached there)
 #ifndef DDIF_EMU
     (void)hipStreamWaitEvent(s, e, 0);
@@ -154,8 +150,7 @@ int Plan::build_backward() {
     DDIF_TRY(tk::linattn_prepare());
 #ifndef DDIF_EMU
     {   // the side stream of the weight gradients (DDIF_TRAIN_STREAMS=0: everything on the caller's stream)
-        const char* env = getenv("DDIF_TRAIN_STREAMS");  // read per plan (a test builds one plan of each kind in one process)
-        const bool two = !env || atoi(env) != 0;
+        const bool two = env_flag("DDIF_TRAIN_STREAMS", true);  // read per plan (a test builds one plan of each kind in one process)
         if (two && !wg_stream) {
             // lowest priority: the gradient chain on the caller's stream is a sequence of small dependent launches -- it should never queue behind
             // the weight gradients' workgroups, which only fill the compute units it leaves idle
@@ -187,7 +182,7 @@ int Plan::build_backward() {
         s.in0 = dy;
         s.in0.st = nullptr;
         s.use_bias = false;
-        s.exact = !train_x3_();
+        s.exact = !train_x3();  // DDIF_TRAIN_X3=0: exact-fp32 MFMA for the dgrad convs (ddif_bwd.cpp)
         s.name = "dgrad";
         if (int e = add_conv(*prog, s, dx)) return e;
         L.v.push_back([this, prog, side](hipStream_t st) {
