@@ -261,6 +261,33 @@ int ddif_plan_forward(ddif_plan_t plan, const float* x, const float* time_host, 
     DDIF_GUARD_END
 }
 
+// ---- test-only stage taps (include/ddif_testops.h)
+int ddif_plan_num_taps(ddif_plan_t plan, int* n) {
+    if (!plan || !n) return ddif::fail(DDIF_ERR_INVALID, "ddif_plan_num_taps: NULL argument");
+    *n = (int)plan->p.taps.size();
+    return DDIF_OK;
+}
+
+int ddif_plan_tap_info(ddif_plan_t plan, int index, const char** name, int* C, int* H, int* W, int* cond_only, int* op) {
+    if (!plan || index < 0 || index >= (int)plan->p.taps.size()) return ddif::fail(DDIF_ERR_INVALID, "ddif_plan_tap_info: bad plan / index");
+    const auto& t = plan->p.taps[index];
+    if (name) *name = t.name.c_str();
+    if (C) *C = t.t.C;
+    if (H) *H = t.t.H;
+    if (W) *W = t.t.W;
+    if (cond_only) *cond_only = t.cond_only ? 1 : 0;
+    if (op) *op = t.op;
+    return DDIF_OK;
+}
+
+int ddif_plan_forward_taps(ddif_plan_t plan, const float* x, const float* time_host, const float* self_cond, float* out, int n_taps, const int* taps,
+                           float* const* tap_out, void* stream) {
+    DDIF_GUARD_BEGIN
+    DDIF_PLAN_ENTER(plan, "ddif_plan_forward_taps");
+    return plan->p.forward_taps(x, time_host, self_cond, out, n_taps, taps, tap_out, (hipStream_t)stream);
+    DDIF_GUARD_END
+}
+
 int ddif_plan_sample_ddpm(ddif_plan_t plan, const ddif_ddpm_tables* tabs, const float* x_T, const float* noise, uint64_t seed,
                           uint64_t tile0, float clamp_lo, float clamp_hi, int do_clamp, float* out, void* stream) {
     DDIF_GUARD_BEGIN

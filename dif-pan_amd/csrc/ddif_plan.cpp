@@ -213,6 +213,13 @@ void Plan::use(const void* p) {
     if (idx < l.first) l.first = idx;
 }
 
+// TEST-ONLY stage tap (ddif_plan.h): `t` is complete and live behind the launch pushed last -- its producer, or, for a tensor produced earlier (a skip
+// connection, a cond-only cache), a launch in front of its last reader.  Inference plans only; the dry pass's records are dropped with its programs.
+void Plan::tap(const std::string& name, const Tensor& t, bool cond_only) {
+    if (train_mode || !t.p) return;
+    taps.push_back(Tap{name, t, (int)(cond_only ? pre.size() : step.size()) - 1, cond_only});
+}
+
 // Two passes over the same builder: the dry pass only records shapes and liveness, the real pass allocates.
 int Plan::build() {
     math_mode = g_math_mode;
@@ -274,6 +281,7 @@ int Plan::build() {
     fake2id.clear();
     pre.clear();
     step.clear();
+    taps.clear();
     cenc.clear();
     cdec.clear();
     drop_sites.clear();
@@ -767,7 +775,8 @@ struct PlanBuilder {
             auto ig = net.vec_absmax.find(a.gamma), ib = net.vec_absmax.find(a.beta);
             const bool okr = ig != net.vec_absmax.end() && ib != net.vec_absmax.end() &&
                              std::sqrt((double)in.C * in.H * in.W) * ig->second + ib->second < DDIF_F16_AMAX;
-            a.wqkv_f16 = (af16 && f16_enabled() && cq->w_f16 && okr) ? cq->w_f16 : nullptr;
+            // ... and the chosen DDIF_ATTN_NW / DDIF_ATTN_SPLIT form has an f16x2 instantiation (ddif_lr.cpp): the pointer says what the launch computes with
+            a.wqkv_f16 = (af16 && f16_enabled() && cq->w_f16 && okr && attn_block_has_f16()) ? cq->w_f16 : nullptr;
         }
         a.wout = co->w_x3;
         a.bout = co->bias ? co->bias : p.zeros;
@@ -779,18 +788,23 @@ struct PlanBuilder {
         if (!a.gamma || !a.beta) return fail(DDIF_ERR_MISSING, "%s: norm weights missing", ap.c_str());
         Op op;
         op.name = "attn_block";
-        op.label = "attn_block (GN + qkv + attention + out + residual) @8x8";
+        op.label = std::string("attn_block (GN + qkv ") + (a.wqkv_f16 ? "f16x2" : "bf16x3") + " + attention + out + residual) @8x8";
+        if (getenv("DDIF_DUMP_PLAN"))  // (its own prefix: the `[ddif plan]` lines are the convs of add_conv, tools/plan_signature.py)
+            fprintf(stderr, "[ddif attn] %-34s qkv=%s split=%d\n", ap.c_str(), a.wqkv_f16 ? "f16x2" : "bf16x3", asplit);
         op.cls = 3;
         op.flop = 2.0 * B * 64 * 128.0 * (384 + 128) + 4.0 * B * 8 * 64.0 * 64 * 16;
         op.bytes = 8.0 * B * 64 * 128;
-        const int ncu = num_cus();
+        int ncu = num_cus();
+        if (g_debug_grid_cap > 0 && g_debug_grid_cap < ncu) ncu = g_debug_grid_cap;  // test hook: workgroups walk several samples / query parts (grid-stride loop)
         op.run = [a, ncu, asplit](hipStream_t s, const StepCtx&) { attn_block_launch(a, a.B * asplit < ncu ? a.B * asplit : ncu, s); };
         step.push_back(std::move(op));
+        p.tap(ap + ".out", *out);
         return 0;
     }
     int self_attention(const std::string& ap, Tensor in, Tensor* out) {
         const PackedConv *cq = PC(ap + ".qkv"), *co = PC(ap + ".out");
         if (!cq || !co) return fail(DDIF_ERR_MISSING, "%s: conv weights missing", ap.c_str());
+        p.tap(ap + ".in", in);
         if (!train && in.H * in.W == 64 && in.C == 128 && x3_enabled() && lr_enabled() && cq->w_x3 && co->w_x3 && cq->ck == 32 && co->ck == 32 && in.st)
             return attn_block(ap, cq, co, in, out);
         // other sizes: three launches
@@ -826,6 +840,7 @@ struct PlanBuilder {
         s2.stats = true;
         s2.name = "attn.out";
         DDIF_TRY(p.add_conv(step, s2, out));
+        p.tap(ap + ".out", *out);
         if (train) {
             Plan::TrainMod& m = tmod(Plan::TrainMod::ATTN, ap, in, *out);
             m.t[0] = qkv;
@@ -1543,11 +1558,16 @@ struct PlanBuilder {
             if (!pq1) return fail(DDIF_ERR_MISSING, "%s.q.1 missing", ci.c_str());
             if (!cur.st || !D.skip.st) return fail(DDIF_ERR_STATE, "%s: prenorm without producer statistics", ci.c_str());
             if (!D.pn_g || !D.pn_b || !D.q0w) return fail(DDIF_ERR_MISSING, "%s: prenorm/q.0 weights missing", ci.c_str());
+            p.tap(ci + ".cur", cur);
+            p.tap(ci + ".skip", D.skip);
+            p.tap(ci + ".cond", p.cdec[lev], true);
             Tensor amix;
             bool fused_attn = false;
             DDIF_TRY(linattn_fused(D, pq1, &amix, &fused_attn));
             if (!fused_attn) DDIF_TRY(linattn_three_launch(D, pq1, &amix));
+            p.tap(ci + ".a", amix);
             DDIF_TRY(ffn(D, amix, &f3));
+            p.tap(ci + ".out", f3);
         }
         DDIF_TRY(resblock(L.p + ".res_block", f3, &cur));
         return attention_if(L);
@@ -1591,15 +1611,22 @@ int Plan::build_impl() {
     for (size_t li = 0; li < net->downs.size(); ++li) {
         const Layer& L = net->downs[li];
         DDIF_TRY(L.kind == L_STEM ? b.stem(li) : (L.kind == L_DOWN ? b.down(li) : b.encoder_block(li)));
+        tap(L.p, b.cur);
         b.feats.push_back(b.cur);
         if (train_mode) {
             tmods.back().pushes_feat = true;
             b.feat_mod.push_back((int)tmods.size() - 1);
         }
     }
-    for (const Layer& L : net->mid) DDIF_TRY(b.mid_block(L));
+    for (const Layer& L : net->mid) {
+        DDIF_TRY(b.mid_block(L));
+        tap(L.p, b.cur);
+    }
     if (train_mode) b.join_side_stream();
-    for (const Layer& L : net->ups) DDIF_TRY(L.kind == L_UP ? b.up(L) : b.decoder_block(L));
+    for (const Layer& L : net->ups) {
+        DDIF_TRY(L.kind == L_UP ? b.up(L) : b.decoder_block(L));
+        tap(L.p, b.cur);
+    }
     DDIF_TRY(b.final_conv());
     DDIF_TRY(ensure_tb(B));
     return 0;
@@ -1838,6 +1865,42 @@ int Plan::forward(const float* x, const float* t_host, const float* sc, float* o
     ctx.tb = tb;
     ctx.tb_stride = net->nslots;
     run_prog(step, s, ctx, false);
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid((size_t)B * HW * C), dim3(256), 0, s, (const float*)net_out.p, B, C, HW, out);
+    DDIF_HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// TEST-ONLY (include/ddif_testops.h ddif_plan_forward_taps): forward() launch by launch -- plain stream launches, no profiling -- with a layout-converting copy
+// (NHWC arena tensor -> caller's NCHW buffer) of every requested tap right behind the launch that completes it: the arena reuses the memory later in the step.
+int Plan::forward_taps(const float* x, const float* t_host, const float* sc, float* out, int n, const int* ids, float* const* dst, hipStream_t s) {
+    if (train_mode) return fail(DDIF_ERR_STATE, "ddif_plan_forward_taps: inference plans only");
+    if (!cond_set) return fail(DDIF_ERR_STATE, "ddif_plan_forward_taps before ddif_plan_set_cond");
+    if (!x || !t_host || !out || n < 0 || (n > 0 && (!ids || !dst))) return fail(DDIF_ERR_INVALID, "ddif_plan_forward_taps: NULL argument");
+    for (int k = 0; k < n; ++k) {
+        if (ids[k] < 0 || ids[k] >= (int)taps.size() || !dst[k]) return fail(DDIF_ERR_INVALID, "ddif_plan_forward_taps: tap %d of %d / NULL buffer", ids[k], (int)taps.size());
+        const Tap& tp = taps[ids[k]];
+        if (tp.op < 0 || tp.op >= (int)(tp.cond_only ? pre.size() : step.size())) return fail(DDIF_ERR_STATE, "ddif_plan_forward_taps: tap %s has no producer", tp.name.c_str());
+    }
+    auto copy_out = [&](int k) {
+        const Tap& tp = taps[ids[k]];
+        hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid((size_t)B * tp.t.H * tp.t.W * tp.t.C), dim3(256), 0, s, (const float*)tp.t.p, B, tp.t.C, tp.t.H * tp.t.W, dst[k]);
+    };
+    const int HW = H * W, Cx = net->cfg.in_channel;
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, ew_grid((size_t)B * HW * Cx), dim3(256), 0, s, x, B, Cx, HW, 0, Cx, x_in.p);
+    if (sc) hipLaunchKernelGGL(nchw_to_nhwc_kernel, ew_grid((size_t)B * HW * C), dim3(256), 0, s, sc, B, C, HW, 0, C, sc_in.p);
+    if (int e = time_rows(t_host, B, s)) return e;
+    for (int k = 0; k < n; ++k)
+        if (taps[ids[k]].cond_only) copy_out(k);  // caches of the set_cond program: complete since set_cond, never aliased
+    StepCtx ctx;
+    ctx.x = x_in.p;
+    ctx.sc = sc ? sc_in.p : x_in.p;
+    ctx.tb = tb;
+    ctx.tb_stride = net->nslots;
+    for (int i = 0; i < (int)step.size(); ++i) {
+        step[i].run(s, ctx);
+        for (int k = 0; k < n; ++k)
+            if (!taps[ids[k]].cond_only && taps[ids[k]].op == i) copy_out(k);
+    }
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid((size_t)B * HW * C), dim3(256), 0, s, (const float*)net_out.p, B, C, HW, out);
     DDIF_HIPCHK(hipGetLastError());
     return 0;

@@ -122,7 +122,8 @@ void dw3x3_plain(hipStream_t s, const float* in, int C, int B, int H, int W, con
 struct AttnBlockArgs;
 int attn_block_prepare();                                                        // ddif_lr.cpp (kernels_attn.h)
 void attn_block_launch(const AttnBlockArgs& a, int grid, hipStream_t s);
-int attn_block_split();  // workgroups per sample (4 since round 6; DDIF_ATTN_SPLIT=1 / 2: one / two)
+int attn_block_split();  // workgroups per sample: 4 by default; DDIF_ATTN_SPLIT=1 / 2: one / two; DDIF_ATTN_NW=8: one
+bool attn_block_has_f16();  // the chosen DDIF_ATTN_NW / DDIF_ATTN_SPLIT form has an f16x2 qkv instantiation (four waves, four workgroups per sample only)
 
 // round 6: ask add_conv() to fold the NEXT block's CondInjection (x_conv + FiLM) into this conv's epilogue (kernels_conv.h EPI_XF); `done` and `out` come back
 struct XfReq {
@@ -233,6 +234,13 @@ struct Plan {
     size_t arena_bytes = 0, unaliased_bytes = 0;
     void use(const void* p);              // dry pass: the launch being created reads or writes p
 
+    // ---- TEST-ONLY stage taps (include/ddif_testops.h ddif_plan_tap_* / ddif_plan_forward_taps): the builder notes, for named stages of an inference plan, the
+    //      tensor and the index of a launch after which it is complete and still live in the arena.  Bookkeeping only: no use(), no allocation, no launch --
+    //      the programs, the arena and every signature of a plan are what they are without it.  forward_taps() copies a tap out right behind that launch.
+    struct Tap { std::string name; Tensor t; int op; bool cond_only; };  // cond_only: written by the set_cond program (persistent), op indexes `pre`
+    std::vector<Tap> taps;
+    void tap(const std::string& name, const Tensor& t, bool cond_only = false);
+    int forward_taps(const float* x, const float* t_host, const float* sc, float* out, int n, const int* ids, float* const* dst, hipStream_t s);
     ~Plan();
     int build();
     int build_impl();

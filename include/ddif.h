@@ -357,7 +357,7 @@ DDIF_API int ddif_plan_range_status(ddif_plan_t plan, void* stream, int* overflo
 DDIF_API int ddif_set_f16_raw(int on);
 DDIF_API int ddif_get_f16_raw(void);
 
-/* TEST HOOK: cap the persistent grid (workgroups per conv launch) of plans created afterwards; 0 removes the cap.
+/* TEST HOOK: cap the persistent grid (workgroups per conv / fused attention launch) of plans created afterwards; 0 removes the cap.
  * Results do not depend on the cap (work items are walked in a fixed order per workgroup and every reduction has a
  * fixed order); tests use it to make small cases walk many work items per workgroup, across sample boundaries,
  * which is the regime the B=64 benchmark configuration runs in. */

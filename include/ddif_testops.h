@@ -109,6 +109,26 @@ DDIF_API int ddif_q_sample(const float* x0, const float* noise, const float* a, 
 /* F.l1_loss(pred, target), mean reduction: out = one device float */
 DDIF_API int ddif_l1_loss_fwd(const float* pred, const float* target, int64_t n, float* out, void* stream);
 
+/* ---- stage taps of an INFERENCE plan ----------------------------------------------------------------------------------------
+ * The fused inference kernels (attn_block_kernel, self_attn_mfma_kernel, linattn_fused_kernel, linattn8_fused_kernel) are reachable through a plan only, and
+ * an end-to-end comparison hardly sees them: GroupNorms and ~30 layers behind the bottleneck damp a wholly wrong attention below the forward tolerance
+ * (tests/test_stage_parity.py).  While it builds a plan, the builder therefore notes named stages -- tensor and the launch after which it is complete:
+ *   "<block>.attn.in" / "<block>.attn.out"            input and output of every SelfAttention site (fused 64-token block or three launches)
+ *   "<block>.cond_inj.cur" / ".skip" / ".cond"        the two inputs of a decoder FastAttnCondInjection and the resized decoder cond image it reads
+ *   "<block>.cond_inj.a"                              attn_out(o) + attn_res(xn): what linattn_fused / linattn8_fused / the three-launch path write
+ *   "<block>.cond_inj.out"                            f + a
+ *   "downs.i" / "mid.i" / "ups.i"                     every layer output
+ * Only tensors that exist in memory are noted, and noting them changes nothing of the plan: launch program, arena and ddif_plan_num_launches are those of a
+ * plan without taps.  Train-mode plans have no taps (their tape keeps every tensor: ddif_plan_train_*). */
+DDIF_API int ddif_plan_num_taps(ddif_plan_t plan, int* n);
+/* name: owned by the plan; C, H, W: the tensor is (B, C, H, W); cond_only: written by ddif_plan_set_cond, not by a step; op: index of the launch (of the step
+ * program, or of the cond-only program) behind which it is read.  Every output pointer nullable. */
+DDIF_API int ddif_plan_tap_info(ddif_plan_t plan, int index, const char** name, int* C, int* H, int* W, int* cond_only, int* op);
+/* ddif_plan_forward, launch by launch (no graph), which copies tap taps[k] into tap_out[k] -- a caller-owned DEVICE buffer of B*C*H*W floats, NCHW fp32 -- right
+ * behind the launch that completes it: the plan's arena reuses the memory later in the same step, so a tap cannot be read once the forward has ended. */
+DDIF_API int ddif_plan_forward_taps(ddif_plan_t plan, const float* x, const float* time_host, const float* self_cond, float* out, int n_taps, const int* taps,
+                                    float* const* tap_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,9 +152,9 @@ def cond_injection(sd, p: str, x: Tensor, cL: Tensor, groups: int) -> Tensor:
     return xc * (1 + scale) + shift
 
 
-def fast_attn_cond_injection(sd, p: str, x: Tensor, cL: Tensor, groups: int, heads: int = 8, path_scale: Optional[Tensor] = None) -> Tensor:
-    """Decoder FastAttnCondInjection (models/sr3_dwt.py:493-577).  path_scale: the DropPath row scale (B,) of the FFN branch (0 or
-    1/(1-p), train mode :534,576); None = eval."""
+def linear_attention_mix(sd, p: str, x: Tensor, cL: Tensor, groups: int, heads: int = 8) -> Tensor:
+    """The linear-attention half of the decoder FastAttnCondInjection (models/sr3_dwt.py:536-573): a = attn_out(o) + attn_res(xn), the tensor the
+    feed-forward half starts from (tests/test_stage_parity.py compares the fused inference kernels with it stage by stage)."""
     B, Cf, H, W = x.shape
     xn = _gn(x, sd, p + ".prenorm_x", groups)
     q = F.conv2d(F.conv2d(xn, sd[p + ".q.0.weight"], None, padding=1, groups=Cf),
@@ -177,6 +177,13 @@ def fast_attn_cond_injection(sd, p: str, x: Tensor, cL: Tensor, groups: int, hea
         a = a + F.conv2d(xn, sd[p + ".attn_res.weight"], sd[p + ".attn_res.bias"])
     else:
         a = a + xn
+    return a
+
+
+def fast_attn_cond_injection(sd, p: str, x: Tensor, cL: Tensor, groups: int, heads: int = 8, path_scale: Optional[Tensor] = None) -> Tensor:
+    """Decoder FastAttnCondInjection (models/sr3_dwt.py:493-577).  path_scale: the DropPath row scale (B,) of the FFN branch (0 or
+    1/(1-p), train mode :534,576); None = eval."""
+    a = linear_attention_mix(sd, p, x, cL, groups, heads)
     f = F.conv2d(a, sd[p + ".ffn.0.weight"], None, padding=1)
     f = F.conv2d(F.silu(f), sd[p + ".ffn.2.weight"], None, padding=1)
     f = F.conv2d(f, sd[p + ".ffn.3.weight"], sd[p + ".ffn.3.bias"])

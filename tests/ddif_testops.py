@@ -57,8 +57,56 @@ def get_lib():
         d.ddif_groupnorm_bwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
         d.ddif_swish_bwd.argtypes = [vp, vp, C.c_int64, vp, vp]
         d.ddif_l1_loss_bwd.argtypes = [vp, vp, C.c_int64, C.c_float, vp, vp]
+        d.ddif_plan_num_taps.argtypes = [vp, C.POINTER(i32)]
+        d.ddif_plan_tap_info.argtypes = [vp, i32, C.POINTER(C.c_char_p)] + [C.POINTER(i32)] * 5
+        d.ddif_plan_forward_taps.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(vp), vp]
         _BOUND.add(id(lib))
     return lib
+
+
+def plan_taps(plan):
+    """The stage taps of an inference plan (include/ddif_testops.h): [(name, C, H, W, cond_only, op)] in the order the builder noted them."""
+    lib = get_lib()
+    n = C.c_int()
+    lib.check(lib.dll.ddif_plan_num_taps(plan.h, C.byref(n)), "ddif_plan_num_taps")
+    out = []
+    for i in range(n.value):
+        name = C.c_char_p()
+        v = [C.c_int() for _ in range(5)]
+        lib.check(lib.dll.ddif_plan_tap_info(plan.h, i, C.byref(name), *[C.byref(x) for x in v]), "ddif_plan_tap_info")
+        out.append((name.value.decode(), v[0].value, v[1].value, v[2].value, bool(v[3].value), v[4].value))
+    return out
+
+
+def plan_forward_taps(plan, x, time, self_cond, names=None):
+    """One eager forward of an inference plan (its cond set) that also returns the named stage tensors, each copied to an NCHW fp32 tensor right behind the
+    launch that completes it: (out, {name: tensor}).  names=None: every tap."""
+    lib = get_lib()
+    taps = plan_taps(plan)
+    index = {t[0]: i for i, t in enumerate(taps)}
+    names = [t[0] for t in taps] if names is None else list(names)
+    missing = [n for n in names if n not in index]
+    if missing:
+        raise DdifError(f"no such tap: {missing}")
+    _check_tensor(lib, x, "x")
+    _check_shape(x, "x", (plan.B, plan.net.in_channel, plan.H, plan.W))
+    x = x.contiguous()
+    sc = None
+    if self_cond is not None:
+        _check_tensor(lib, self_cond, "self_cond")
+        _check_shape(self_cond, "self_cond", (plan.B, plan.net.out_channel, plan.H, plan.W))
+        sc = self_cond.contiguous()
+    t = time.detach().to("cpu", torch.float32).reshape(-1)
+    t = (t if t.numel() == plan.B else t.expand(plan.B)).contiguous()
+    out = torch.empty((plan.B, plan.net_out_channels, plan.H, plan.W), dtype=torch.float32, device=x.device)
+    bufs = [torch.empty((plan.B,) + taps[index[n]][1:4], dtype=torch.float32, device=x.device) for n in names]
+    ids = (C.c_int * len(names))(*[index[n] for n in names])
+    ptrs = (C.c_void_p * len(names))(*[b.data_ptr() for b in bufs])
+    lib.check(lib.dll.ddif_plan_forward_taps(plan.h, _ptr(x), C.c_void_p(t.data_ptr()), _ptr(sc), _ptr(out), len(names), ids, ptrs, _stream(lib, x.device)),
+              "ddif_plan_forward_taps")
+    if x.device.type == "cuda":
+        torch.cuda.synchronize(x.device)
+    return out, dict(zip(names, bufs))
 
 
 class Conv3x3Backward:

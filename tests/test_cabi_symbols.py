@@ -23,6 +23,9 @@ def test_header_declares_the_documented_surface():
     # the product surface carries no per-op training-tape entry point any more (round 6): those live in include/ddif_testops.h
     assert not [n for n in names if n.startswith(("ddif_convfwd_", "ddif_convbwd_", "ddif_blockbwd_")) or n.endswith(("_fwd", "_bwd"))]
     assert "ddif_convbwd_run" in _declared("ddif_testops.h") and "ddif_groupnorm_fwd" in _declared("ddif_testops.h")
+    # ... nor the stage taps of inference plans (tests/test_stage_parity.py): test-only as well
+    for tap in ("ddif_plan_num_taps", "ddif_plan_tap_info", "ddif_plan_forward_taps"):
+        assert tap in _declared("ddif_testops.h") and tap not in names
     # ... and the product package binds none of them
     from ddif import runtime
 

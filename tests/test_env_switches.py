@@ -83,6 +83,35 @@ def test_forward_goldens_under_placement_switch(env):
     assert " passed" in r.stdout and "no tests ran" not in r.stdout, tail
 
 
+# The attention STAGES under the switches that pick their kernels (tests/test_stage_parity.py: each stage against the fp64 oracle on its own tapped input -- the
+# forward goldens above cannot see a wrong attention).  The same mechanism: a fresh child process per setting (one switch each: a child that runs one 64 x 64
+# forward costs ~5 s), a time limit on each.  A child that fails, dies or runs into its time limit fails its test with its output shown, and no further child is
+# started: whatever took it down must not be handed the GPU again.
+STAGE_SETTINGS = [{"DDIF_ATTN_NW": "8"}, {"DDIF_ATTN_SPLIT": "1"}, {"DDIF_ATTN_SPLIT": "2"}, {"DDIF_ATTN_F16": "0"}, {"DDIF_LAFUSE": "0"}, {"DDIF_LA8": "0"},
+                  {"DDIF_LA6": "0"}, {"DDIF_LA_NW": "4"}, {"DDIF_LA_NW": "8"}]
+_stage_child_lost = []
+
+
+@pytest.mark.parametrize("env", STAGE_SETTINGS, ids=["+".join("%s=%s" % (k[5:], v) for k, v in e.items()) for e in STAGE_SETTINGS])
+def test_attention_stages_under_switch(env):
+    if _stage_child_lost:
+        pytest.fail("not started: the child under %s did not end well" % _stage_child_lost[0])
+    e = dict(os.environ)
+    e.update(env)
+    try:
+        r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_stage_parity.py"), "-m", "gpu", "-x", "-q", "-s",
+                            "-k", "on_the_gpu and wv3_64_b2 and stressed", "-p", "no:cacheprovider"], env=e, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    except subprocess.TimeoutExpired as ex:
+        _stage_child_lost.append(env)
+        pytest.fail("time limit: %s" % ((ex.stdout or b"")[-3000:],))
+    print("".join(ln + "\n" for ln in r.stdout.splitlines() if ln.startswith("gpu ")))  # the stage rows (e_ref, error, ratio) of this setting
+    tail = (r.stdout + r.stderr)[-6000:]
+    if r.returncode != 0 or " passed" not in r.stdout or "no tests ran" in r.stdout:
+        _stage_child_lost.append(env)
+    assert r.returncode == 0, tail
+    assert " passed" in r.stdout and "no tests ran" not in r.stdout, tail
+
+
 @pytest.mark.parametrize("env", [{"DDIF_X3": "0"}, {"DDIF_LR": "0"}], ids=["X3=0", "LR=0"])
 def test_multi_item_path_under_switch(env):
     """The capped-grid tests once more with DDIF_X3=0 / DDIF_LR=0 (other kernel instantiations, other tile shapes)."""
