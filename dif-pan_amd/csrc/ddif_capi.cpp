@@ -335,6 +335,21 @@ int ddif_plan_get_objective(ddif_plan_t plan, int* pred_mode, int* loss_type) {
     return DDIF_OK;
 }
 
+int ddif_plan_set_threshold(ddif_plan_t plan, int mode, float ratio, float max_val) {
+    DDIF_GUARD_BEGIN
+    DDIF_PLAN_ENTER(plan, "ddif_plan_set_threshold");
+    return plan->p.set_threshold(mode, ratio, max_val);
+    DDIF_GUARD_END
+}
+
+int ddif_plan_get_threshold(ddif_plan_t plan, int* mode, float* ratio, float* max_val) {
+    if (!plan) return ddif::fail(DDIF_ERR_INVALID, "ddif_plan_get_threshold: NULL plan");
+    if (mode) *mode = plan->p.thr_mode;
+    if (ratio) *ratio = plan->p.thr_ratio;
+    if (max_val) *max_val = plan->p.thr_max;
+    return DDIF_OK;
+}
+
 int ddif_plan_sample_ddpm_ex(ddif_plan_t plan, const ddif_ddpm_tables* tabs, const ddif_pred_tables* pred, const float* x_T, const float* noise, uint64_t seed,
                              uint64_t tile0, float clamp_lo, float clamp_hi, int do_clamp, float* out, void* stream) {
     DDIF_GUARD_BEGIN

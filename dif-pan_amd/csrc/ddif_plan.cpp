@@ -6,6 +6,7 @@
 #include "kernels_conv.h"
 #include "kernels_misc.h"
 #include "attn_args.h"
+#include "quantile_args.h"
 #include "kernels_lafuse.h"
 
 namespace ddif {
@@ -1730,6 +1731,27 @@ int Plan::set_objective(int pred, int loss) {
     loss_type = loss;
     return 0;
 }
+// ---- dynamic thresholding (include/ddif.h ddif_plan_set_threshold)
+int Plan::set_threshold(int mode, float ratio, float max_val) {
+    if (mode != DDIF_THRESHOLD_OFF && mode != DDIF_THRESHOLD_DDPM && mode != DDIF_THRESHOLD_SOLVER)
+        return fail(DDIF_ERR_INVALID, "ddif_plan_set_threshold: mode %d (0 off, 1 DDPM form, 2 solver form)", mode);
+    if (mode != DDIF_THRESHOLD_OFF) {
+        if (!(ratio >= 0.f && ratio <= 1.f)) return fail(DDIF_ERR_INVALID, "ddif_plan_set_threshold: ratio %g outside [0, 1]", (double)ratio);
+        if (!(max_val >= 0.f) || max_val > 3.0e38f) return fail(DDIF_ERR_INVALID, "ddif_plan_set_threshold: max_val %g must be finite and >= 0", (double)max_val);
+        if ((long long)H * W * C > 0x7fffffffLL) return fail(DDIF_ERR_INVALID, "ddif_plan_set_threshold: more than 2^31 values per sample");
+        if (int e = quantile_prepare()) return e;
+        if (!d_thr)
+            if (int e = dalloc(&d_thr, (size_t)B)) return e;
+    } else {
+        ratio = 0.f;
+        max_val = 1.f;
+    }
+    if (mode != thr_mode || ratio != thr_ratio || max_val != thr_max) drop_graphs();  // the captured pair holds the other tail / the old rank and floor
+    thr_mode = mode;
+    thr_ratio = ratio;
+    thr_max = max_val;
+    return 0;
+}
 // device copies of the caller's per-sample rows (host or device source, like sqrt_ac / sqrt_1mac)
 int Plan::objective_rows(const ddif_objective_rows* rows, bool need_p2, hipStream_t s) {
     const bool need_rec = pred_mode != DDIF_PRED_X_START;
@@ -1972,7 +1994,23 @@ int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int 
             DDIF_HIPCHK(hipMemcpyAsync(d_tabs + (size_t)(6 + i) * tabs_cap, pt[i], (size_t)n_steps * sizeof(float), hipMemcpyHostToDevice, s));
         }
     }
-    const bool fused = pred ? final_fused_pred : final_fused;
+    // dynamic thresholding (DDPM only, and only where the reference clips at all: p_sample_loop's clip_noise gates both clamps, :447; ddim_sample never clamps
+    // dynamically): s_b needs the whole sample, which the final conv's epilogue cannot see -> the unfused tail with the quantile kernel in front of the update
+    const bool dyn = thr_mode == DDIF_THRESHOLD_DDPM && kind == 0 && do_clamp;
+    if (kind == 0 && graph_exec[0] && graph_dyn != dyn) drop_graphs();
+    const bool fused = !dyn && (pred ? final_fused_pred : final_fused);
+    QuantArgs qa{};
+    if (dyn) {
+        qa.a = net_out.p;
+        qa.lms = lms.p;
+        qa.n = (long long)HW * C;
+        qa.form = QUANT_DDPM;
+        qa.pred = pred ? 1 : 0;
+        qa.run = reinterpret_cast<const SamplerRun*>(d_run);
+        quantile_rank(thr_ratio, qa.n, &qa.k_lo, &qa.k_hi, &qa.w);
+        qa.max_val = thr_max;
+        qa.s_out = d_thr;
+    }
     DDIF_HIPCHK(hipMemcpyAsync(d_run, &run, sizeof(run), hipMemcpyHostToDevice, s));
     DDIF_HIPCHK(hipMemsetAsync(d_step, 0, 2 * sizeof(int), s));
     // the host copies above must have been consumed before `run` (stack) goes away: pageable H2D copies are staged
@@ -2003,6 +2041,13 @@ int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int 
         a.pred = pred ? 1 : 0;
         if (fused) return;  // the update ran in the final conv's epilogue, which also wrote the next step's counter
         a.step = d_step + parity;
+        if (dyn) {
+            QuantArgs q = qa;
+            q.xt = img[parity];
+            q.step = d_step + parity;
+            quantile_launch(q, B, st);
+            a.thr = d_thr;
+        }
         if (kind == 0) hipLaunchKernelGGL(ddpm_step_kernel, ew_grid(n), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(ddim_step_kernel, ew_grid(n), dim3(256), 0, st, a);
         hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, st, (const int*)(d_step + parity), d_step + (parity ^ 1));
@@ -2025,8 +2070,10 @@ int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int 
             hipGraphExec_t ge = nullptr;
             if (e1 == hipSuccess && g) e1 = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
             if (g) (void)hipGraphDestroy(g);
-            if (e1 == hipSuccess && ge) graph_exec[kind] = ge;
-            else {
+            if (e1 == hipSuccess && ge) {
+                graph_exec[kind] = ge;
+                if (kind == 0) graph_dyn = dyn;
+            } else {
                 (void)hipGetLastError();
                 use_graph = false;  // capture unsupported here: plain stream launches (same kernels, same results)
             }
@@ -2146,6 +2193,9 @@ int Plan::sample_dpmpp(const ddif_dpm_tables* t, const float* xT, float lo, floa
     if (!t || t->n_evals < 1 || t->order < 1 || t->order > 3 || !t->t_model || !t->alpha || !t->sigma || !t->ord || !t->cx || !t->a_phi1 || !xT || !out)
         return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpmpp: bad tables");
     if (int e = check_sampler_net(net)) return e;
+    const bool dyn = thr_mode == DDIF_THRESHOLD_SOLVER;
+    if (dyn && do_clamp)
+        return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpmpp: the plan thresholds dynamically (ddif_plan_set_threshold mode 2) -- the image-space clamp is the other corrector, not an addition");
     if (side_pending) {
         train_join(s);
         side_pending = false;
@@ -2154,6 +2204,16 @@ int Plan::sample_dpmpp(const ddif_dpm_tables* t, const float* xT, float lo, floa
     const size_t n = (size_t)B * HW * C;
     hipLaunchKernelGGL(nchw_to_nhwc_kernel, ew_grid(n), dim3(256), 0, s, xT, B, C, HW, 0, C, img[0]);
     if (int e = time_rows(t->t_model, t->n_evals, s)) return e;
+    QuantArgs qa{};
+    if (dyn) {
+        qa.a = net_out.p;
+        qa.n = (long long)HW * C;
+        qa.form = QUANT_DPM;
+        qa.pred = pred_mode;
+        quantile_rank(thr_ratio, qa.n, &qa.k_lo, &qa.k_hi, &qa.w);
+        qa.max_val = thr_max;
+        qa.s_out = d_thr;
+    }
     int cur = 0;
     float* hist[3] = {nullptr, nullptr, nullptr};  // newest first
     int nhist = 0, slot = 0;
@@ -2165,8 +2225,15 @@ int Plan::sample_dpmpp(const ddif_dpm_tables* t, const float* xT, float lo, floa
         run_prog(step, s, ctx, prof);
         float* mnew = mbuf[slot];
         slot = (slot + 1) % 3;
+        if (dyn) {  // s_b of this evaluation's x0 (solver/dpm_solver.py:424-433), on the device: nothing comes back to the host
+            QuantArgs q = qa;
+            q.xt = img[cur];
+            q.alpha = t->alpha[k];
+            q.sigma = t->sigma[k];
+            quantile_launch(q, B, s);
+        }
         hipLaunchKernelGGL(dpm_x0_kernel, ew_grid(n), dim3(256), 0, s, (const float*)net_out.p, (const float*)img[cur], (const float*)lms.p,
-                           t->alpha[k], t->sigma[k], lo, hi, do_clamp, pred_mode, n, mnew);
+                           t->alpha[k], t->sigma[k], lo, hi, do_clamp, pred_mode, n, mnew, (const float*)(dyn ? d_thr : nullptr), (size_t)HW * C);
         hist[2] = hist[1];
         hist[1] = hist[0];
         hist[0] = mnew;

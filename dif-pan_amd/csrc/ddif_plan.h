@@ -198,6 +198,12 @@ struct Plan {
     // objective (ddif_plan_set_objective; sticky): what the network output means and which loss the training step takes.  Defaults = the engine's.
     int pred_mode = DDIF_PRED_X_START, loss_type = DDIF_LOSS_L1;
     int set_objective(int pred, int loss);
+    // dynamic thresholding (ddif_plan_set_threshold; sticky): 0 off, 1 the DDPM form (clamp(v, 0, s) / s around lms), 2 the solver form (clamp(x0, -s, s) / s)
+    int thr_mode = DDIF_THRESHOLD_OFF;
+    float thr_ratio = 0.f, thr_max = 1.f;
+    float* d_thr = nullptr;             // [B] per-sample s of the current step, written by quantile_abs_kernel (kernels_quantile.h), read by the step kernel behind it
+    bool graph_dyn = false;             // the captured DDPM pair holds the thresholding tail (unfused: quantile, update, counter)
+    int set_threshold(int mode, float ratio, float max_val);
     bool final_fused = false;           // the final conv carries the sampler epilogue: no separate update / counter launches in the DDPM / DDIM loops
     int math_mode = 0;                  // g_math_mode / g_f16_raw at creation: one plan is built under ONE arithmetic even when the process-wide switches change while it builds
     int f16_raw = 1;

@@ -779,6 +779,7 @@ struct StepArgs {
     const SamplerRun* run;
     const int* step;
     int pred;          // 1: x0 holds the noise / v prediction -> pred_x0 with tables 6 / 7 in front of the clamp (:369-375); 0: x_start
+    const float* thr;  // DDPM, dynamic thresholding (:327-344, 397-398): per-sample s_b = max(quantile(|x0 + lms|, p), max_val) from quantile_abs_kernel, or null = the absolute clamp
 };
 __global__ void step_advance_kernel(const int* cur, int* next) { *next = *cur + 1; }  // double-buffered counters: nobody reads `next` during this step
 
@@ -800,7 +801,12 @@ __global__ void ddpm_step_kernel(StepArgs a) {
         if (a.pred) x0 = pred_x0(px, a.img[i], po, x0);
         if (r.do_clamp) {
             const float l = a.lms[i];
-            x0 = fminf(fmaxf(x0 + l, r.lo), r.hi) - l;
+            if (a.thr) {  // clamp(v, 0, s_b) / s_b: the reference keeps the lower bound 0 here (:341-343)
+                const float sb = a.thr[b];
+                x0 = fminf(fmaxf(x0 + l, 0.f), sb) / sb - l;
+            } else {
+                x0 = fminf(fmaxf(x0 + l, r.lo), r.hi) - l;
+            }
         }
         const size_t e = (b * a.C + c) * a.HW + p;
         const float z = noise ? noise[e] : philox_normal(r.seed, (unsigned)(k + 1), (r.tile0 * a.C * a.HW) + e);
@@ -844,8 +850,9 @@ __global__ void ddim_step_kernel(StepArgs a) {
 // DPM-Solver++ data prediction (solver/dpm_solver.py:298-300,441-450): the x_start -> eps -> x_start round trip of
 // model_wrapper + data_prediction_fn, then the image-space clamp corrector (diffusion_engine.py:43-49).
 // model_type (solver/dpm_solver.py:296-303; the plan's pred_mode): 0 "x_start" eps = (x - alpha o) / sigma, 1 "noise" eps = o, 2 "v" eps = alpha o + sigma x.
+// thr (nullable): dynamic thresholding instead (:424-433, exclusive with the clamp), x0 = clamp(x0, -s_b, s_b) / s_b with s_b from quantile_abs_kernel, `per` values per sample.
 __global__ void dpm_x0_kernel(const float* net, const float* x, const float* lms, float alpha, float sigma, float lo,
-                              float hi, int do_clamp, int model_type, size_t total, float* x0_out) {
+                              float hi, int do_clamp, int model_type, size_t total, float* x0_out, const float* thr, size_t per) {
 #pragma clang fp contract(off)
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const float xv = x[i], o = net[i];
@@ -860,6 +867,9 @@ __global__ void dpm_x0_kernel(const float* net, const float* x, const float* lms
         if (do_clamp) {
             const float l = lms[i];
             x0 = fminf(fmaxf(x0 + l, lo), hi) - l;
+        } else if (thr) {
+            const float sb = thr[i / per];
+            x0 = fminf(fmaxf(x0, -sb), sb) / sb;
         }
         x0_out[i] = x0;
     }

@@ -7,8 +7,9 @@ loops do not run in Python: `p_sample_loop` / `ddim_sample_loop` hand the per-st
 hand-written gfx950 kernels on the current stream.
 
 Implemented: conditional models, pred_mode "x_start" / "noise" / "pred_v" (samplers, p_losses, the native training step),
-clamp_type="abs", loss "l1" / "l2" (value and backward pass), p2 loss weighting.  Still refused (DdifError, no fallback):
-unconditional models, clamp_type="dynamic", loss_type="l1ssim", get_interm_fm.
+clamp_type="abs" and "dynamic" (Imagen's dynamic thresholding in the DDPM loop: an exact per-sample quantile kernel in front of the update,
+`ddif_plan_set_threshold`), loss "l1" / "l2" (value and backward pass), p2 loss weighting.  Still refused (DdifError, no fallback):
+unconditional models, loss_type="l1ssim", get_interm_fm.
 """
 from __future__ import annotations
 
@@ -166,11 +167,15 @@ class GaussianDiffusion(nn.Module):
     def _plan(self, cond: torch.Tensor, train: bool = False):
         if not self.conditional:
             raise DdifError("unconditional sampling is not implemented by the HIP path")
-        if self.clamp_type != "abs":
-            raise DdifError("clamp_type='dynamic' is not implemented by the HIP path")
         B, _, H, W = cond.shape
         plan = self.model.plan_for(B, H, W, cond.device, train=train)
         plan.set_objective(self.pred_mode, self.loss_type)  # sticky on the (cached) plan: every entry below states it
+        # ... and the clamp of the DDPM loop (:391-399).  The two attributes are read here, at call time, as the reference's dynamic_thresholding_fn reads them
+        # (:333, :337).  The library applies it where the reference does: p_sample_loop with a clamp_range; p_losses and the DDIM loop never see it.
+        if self.clamp_type == "dynamic":
+            plan.set_threshold("ddpm", float(self.dynamic_thresholding_ratio), float(self.thresholding_max_val))
+        else:
+            plan.set_threshold("off")
         plan.set_cond(cond)
         return plan
 
@@ -228,6 +233,13 @@ class GaussianDiffusion(nn.Module):
     def predict_noise_from_start(self, x_t, t, x_0_pred):
         return ((extract(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t - x_0_pred)
                 / extract(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape))
+
+    def dynamic_thresholding_fn(self, x0, t=None):
+        """Reference :327-344 on device tensors: s = max(quantile(|x0_b|, dynamic_thresholding_ratio), thresholding_max_val) per sample, then
+        clamp(x0, 0, s) / s -- the lower bound is 0, as in the reference.  One selection kernel + one elementwise kernel of libddif."""
+        from ..runtime import dynamic_threshold
+
+        return dynamic_threshold(x0, float(self.dynamic_thresholding_ratio), float(self.thresholding_max_val), symmetric=False)[0]
 
     def q_posterior(self, x_start, x_t, t):
         mean = (extract(self.posterior_mean_coef1, t, x_t.shape) * x_start

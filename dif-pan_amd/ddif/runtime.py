@@ -61,6 +61,7 @@ class ObjectiveRows(C.Structure):
 
 PRED_MODES = {"x_start": 0, "noise": 1, "pred_v": 2, "v": 2}  # GaussianDiffusion's names + model_wrapper's "v" (include/ddif.h DDIF_PRED_*)
 LOSS_TYPES = {"l1": 0, "l2": 1}
+THRESHOLD_MODES = {"off": 0, "ddpm": 1, "solver": 2}  # include/ddif.h DDIF_THRESHOLD_*
 
 
 class ProfResult(C.Structure):
@@ -119,6 +120,9 @@ class _Lib:
         d.ddif_plan_q_sample_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         d.ddif_plan_set_objective.argtypes = [vp, i32, i32]
         d.ddif_plan_get_objective.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+        d.ddif_plan_set_threshold.argtypes = [vp, i32, f32, f32]
+        d.ddif_plan_get_threshold.argtypes = [vp, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32)]
+        d.ddif_dynamic_threshold.argtypes = [vp, i32, C.c_int64, f32, f32, i32, vp, vp, vp]
         d.ddif_plan_sample_ddpm_ex.argtypes = [vp, C.POINTER(DdpmTables), C.POINTER(PredTables), vp, vp, u64, u64, f32, f32, i32, vp, vp]
         d.ddif_plan_sample_ddim_ex.argtypes = [vp, C.POINTER(DdimTables), C.POINTER(PredTables), vp, vp, u64, u64, f32, f32, i32, vp, vp]
         d.ddif_plan_q_sample_forward_ex.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(ObjectiveRows), vp, vp, vp]
@@ -377,6 +381,7 @@ class PlanHandle:
         self._cond_ver = None
         self.net_out_channels = net.out_channel
         self.objective = ("x_start", "l1")
+        self.threshold = ("off", 0.0, 1.0)
 
     def _create(self):
         h = C.c_void_p()
@@ -398,6 +403,27 @@ class PlanHandle:
         if obj != ("x_start", "l1"):  # a rebuilt plan (range fallback) keeps its objective
             self.objective = ("x_start", "l1")
             self.set_objective(*obj)
+        thr = getattr(self, "threshold", ("off", 0.0, 1.0))
+        if thr[0] != "off":  # ... and its thresholding
+            self.threshold = ("off", 0.0, 1.0)
+            self.set_threshold(*thr)
+
+    def set_threshold(self, mode: str = "off", ratio: float = 0.0, max_val: float = 1.0):
+        """Dynamic thresholding of the samplers (include/ddif.h ddif_plan_set_threshold; sticky): "off" | "ddpm" (GaussianDiffusion clamp_type="dynamic":
+        clamp(x0 + lms, 0, s) / s - lms) | "solver" (DPM_Solver correcting_x0_fn="dynamic_thresholding": clamp(x0, -s, s) / s), with
+        s = max(quantile(|.|, ratio), max_val) per sample and step."""
+        if mode not in THRESHOLD_MODES:
+            raise DdifError(f"threshold mode {mode!r}: expected one of {sorted(THRESHOLD_MODES)}")
+        thr = (mode, 0.0, 1.0) if mode == "off" else (mode, float(ratio), float(max_val))
+        if thr != self.threshold:
+            self.lib.check(self.lib.dll.ddif_plan_set_threshold(self.h, THRESHOLD_MODES[thr[0]], thr[1], thr[2]), "ddif_plan_set_threshold")
+            self.threshold = thr
+
+    def get_threshold(self):
+        """(mode, ratio, max_val) as the LIBRARY holds them for this plan (include/ddif.h ddif_plan_get_threshold)."""
+        m, r, v = C.c_int(), C.c_float(), C.c_float()
+        self.lib.check(self.lib.dll.ddif_plan_get_threshold(self.h, C.byref(m), C.byref(r), C.byref(v)), "ddif_plan_get_threshold")
+        return ({v_: k for k, v_ in THRESHOLD_MODES.items()}[m.value], r.value, v.value)
 
     def set_objective(self, pred_mode: str = "x_start", loss_type: str = "l1"):
         """What the network output means to the samplers / p_losses and which loss the training step takes (include/ddif.h
@@ -769,6 +795,23 @@ def cond_assemble(lms_raw: torch.Tensor, pan_raw: torch.Tensor, division: float,
     lib.check(lib.dll.ddif_cond_assemble(_ptr(lms_raw), _ptr(pan_raw), float(division), B, Cc, P, H, W, int(wavelet_order), _ptr(out),
                                          _stream(lib, lms_raw.device)), "ddif_cond_assemble")
     return out
+
+
+def dynamic_threshold(x0: torch.Tensor, ratio: float, max_val: float, symmetric: bool):
+    """Imagen's dynamic thresholding of a batch (include/ddif.h ddif_dynamic_threshold): per sample s = max(quantile(|x0_b|, ratio), max_val) by an exact
+    selection on the device, then clamp(x0, -s if symmetric else 0, s) / s.  Returns (thresholded x0, s of shape (B,))."""
+    lib = get_lib()
+    _check_tensor(lib, x0, "x0")
+    _check_current_device(x0, "x0")
+    if x0.dim() < 1 or x0.numel() == 0:
+        raise DdifError(f"x0: expected a non-empty batch, got shape {tuple(x0.shape)}")
+    x = x0.contiguous()
+    B = x.shape[0]
+    out = torch.empty_like(x)
+    s = torch.empty((B,), dtype=torch.float32, device=x.device)
+    lib.check(lib.dll.ddif_dynamic_threshold(_ptr(x), B, x.numel() // B, float(ratio), float(max_val), 1 if symmetric else 0, _ptr(out), _ptr(s),
+                                             _stream(lib, x.device)), "ddif_dynamic_threshold")
+    return out, s
 
 
 def metrics(gt: torch.Tensor, pred: torch.Tensor, ergas_ratio: float = 4.0) -> torch.Tensor:

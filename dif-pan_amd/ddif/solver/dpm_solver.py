@@ -4,10 +4,11 @@ reaches: `NoiseScheduleVP('discrete')` (:6-175), `model_wrapper` (:178-342) and 
 
 Scalar schedule math stays on the host as fp32 torch scalars (the reference evaluates the same expressions as 0-d /
 1-element fp32 tensors); the tensor work of a whole sampling run -- every network evaluation, the x_start<->eps
-round trip, the corrector clamp and the multistep updates -- is ONE call into libddif (`ddif_plan_sample_dpmpp`)
+round trip, the corrector (the image-space clamp or dynamic thresholding, whose per-sample quantile is a selection
+kernel in front of the data prediction) and the multistep updates -- is ONE call into libddif (`ddif_plan_sample_dpmpp`)
 when the model is a ddif `UNetSR3`.  Any other model / corrector takes the generic loop below (same algorithm, model
-called per evaluation).  Out of scope and rejected loudly: continuous schedules, singlestep / adaptive solvers,
-classifier guidance, dynamic thresholding.
+called per evaluation; dynamic thresholding there is the stateless `ddif_dynamic_threshold`).  Out of scope and rejected
+loudly: continuous schedules, singlestep / adaptive solvers, classifier guidance.
 """
 from __future__ import annotations
 
@@ -123,18 +124,23 @@ class DPM_Solver:
     def __init__(self, model_fn, noise_schedule, algorithm_type="dpmsolver++", correcting_x0_fn=None,
                  correcting_xt_fn=None, thresholding_max_val=1.0, dynamic_thresholding_ratio=0.995):
         assert algorithm_type in ["dpmsolver", "dpmsolver++"]
-        if correcting_x0_fn == "dynamic_thresholding":
-            raise DdifError("dynamic thresholding is out of scope of the HIP path")
         self._model_fn = model_fn
         self.model = lambda x, t: model_fn(x, t.expand((x.shape[0])))
         self.noise_schedule = noise_schedule
         self.algorithm_type = algorithm_type
-        self.correcting_x0_fn = correcting_x0_fn
+        self.correcting_x0_fn = self.dynamic_thresholding_fn if correcting_x0_fn == "dynamic_thresholding" else correcting_x0_fn  # reference :417-420
         self.correcting_xt_fn = correcting_xt_fn
         self.dynamic_thresholding_ratio = dynamic_thresholding_ratio
         self.thresholding_max_val = thresholding_max_val
 
     # ---- reference helpers kept for API compatibility ---------------------------------------------------------------
+    def dynamic_thresholding_fn(self, x0, t=None):
+        """Reference :424-433 on device tensors: s = max(quantile(|x0_b|, dynamic_thresholding_ratio), thresholding_max_val) per sample, then
+        clamp(x0, -s, s) / s.  One selection kernel + one elementwise kernel of libddif."""
+        from ..runtime import dynamic_threshold
+
+        return dynamic_threshold(x0, float(self.dynamic_thresholding_ratio), float(self.thresholding_max_val), symmetric=True)[0]
+
     def noise_prediction_fn(self, x, t):
         return self.model(x, t)
 
@@ -200,7 +206,8 @@ class DPM_Solver:
         return v
 
     def _fused_target(self):
-        """(UNetSR3, cond, clamp) when the whole run can execute inside libddif, else None."""
+        """(UNetSR3, cond, clamp) when the whole run can execute inside libddif, else None.  clamp: None, (lo, hi) of an ImageSpaceClamp, or the
+        string "dynamic" for this solver's own dynamic_thresholding_fn (the plan's threshold mode "solver")."""
         meta = getattr(self._model_fn, "ddif", None)
         if meta is None or self.algorithm_type != "dpmsolver++" or self.correcting_xt_fn is not None:
             return None
@@ -213,6 +220,8 @@ class DPM_Solver:
         cx0 = self.correcting_x0_fn
         if cx0 is None:
             return meta["model"], meta["condition"], None
+        if getattr(cx0, "__func__", None) is DPM_Solver.dynamic_thresholding_fn and getattr(cx0, "__self__", None) is self:
+            return meta["model"], meta["condition"], "dynamic"
         if isinstance(cx0, ImageSpaceClamp):
             cond, C = meta["condition"], meta["model"].cfg["out_channel"]
             if cx0.lms.shape == cond[:, :C].shape and cx0.lms.data_ptr() == cond[:, :C].data_ptr() or \
@@ -252,6 +261,11 @@ class DPM_Solver:
             B, _, H, W = x.shape
             plan = model.plan_for(B, H, W, x.device)
             plan.set_objective(self._model_fn.ddif["model_type"], plan.objective[1])  # the model_type branch of model_wrapper (reference :296-303) runs in dpm_x0_kernel
+            if clamp == "dynamic":  # the two attributes are read here, at call time, as the reference's dynamic_thresholding_fn reads them
+                plan.set_threshold("solver", float(self.dynamic_thresholding_ratio), float(self.thresholding_max_val))
+                clamp = None
+            else:
+                plan.set_threshold("off")
             plan.set_cond(cond)
             tabs = dict(n_evals=steps, order=order,
                         t_model=[float((ts[k] - 1.0 / ns.total_N) * 1000.0) for k in range(steps)],

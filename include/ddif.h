@@ -191,6 +191,30 @@ DDIF_API int ddif_plan_sample_ddpm_ex(ddif_plan_t plan, const ddif_ddpm_tables* 
 DDIF_API int ddif_plan_sample_ddim_ex(ddif_plan_t plan, const ddif_ddim_tables* tabs, const ddif_pred_tables* pred, const float* x_T, const float* noise,
                                       uint64_t seed, uint64_t tile0, float clamp_lo, float clamp_hi, int do_clamp, float* out, void* stream);
 
+/* ---- dynamic thresholding (Imagen) ------------------------------------------------------------------------------------- */
+
+/* GaussianDiffusion(clamp_type="dynamic") (diffusion/diffusion_ddpm_pan.py:327-344, 391-399) and DPM_Solver(correcting_x0_fn="dynamic_thresholding")
+ * (solver/dpm_solver.py:424-433).  Per step and per sample b:  s_b = max(quantile(|v_b|, ratio), max_val)  over all C*H*W values of the sample, with
+ * torch.quantile's linear interpolation between the two neighbouring order statistics (rank fp32(ratio) * fp32(n - 1), evaluated as ATen does for fp32
+ * input).  The quantile is an exact selection on the device (csrc/kernels_quantile.h), one launch in front of the update; nothing goes through the host.
+ * Sticky per plan, like the objective:
+ *   DDIF_THRESHOLD_OFF (default): every entry point behaves exactly as before.
+ *   DDIF_THRESHOLD_DDPM: ddif_plan_sample_ddpm[_ex] with do_clamp != 0 replaces the absolute clamp by
+ *       v = x0 + lms;  x0 = clamp(v, 0, s_b) / s_b - lms        (the LOWER BOUND IS 0, as in the reference, :341-343; clamp_lo / clamp_hi are ignored)
+ *     and runs the update as its own launch behind the quantile kernel (the final conv's sampler epilogue cannot see a whole sample).  do_clamp == 0
+ *     disables it too (p_sample_loop's clip_noise gates both clamps, :447).  No effect on ddif_plan_sample_ddim (ddim_sample never clamps dynamically).
+ *   DDIF_THRESHOLD_SOLVER: ddif_plan_sample_dpmpp applies  x0 = clamp(x0, -s_b, s_b) / s_b  to every data prediction; do_clamp must be 0 (the
+ *     image-space clamp is the other corrector, DDIF_ERR_INVALID otherwise).  No effect on the DDPM / DDIM loops.
+ * ratio in [0, 1], max_val finite and >= 0 (both ignored for DDIF_THRESHOLD_OFF); DDIF_ERR_INVALID otherwise. */
+#define DDIF_THRESHOLD_OFF 0
+#define DDIF_THRESHOLD_DDPM 1
+#define DDIF_THRESHOLD_SOLVER 2
+DDIF_API int ddif_plan_set_threshold(ddif_plan_t plan, int mode, float ratio, float max_val);
+DDIF_API int ddif_plan_get_threshold(ddif_plan_t plan, int* mode, float* ratio, float* max_val);
+/* The stateless op (dynamic_thresholding_fn of both classes): x, out (nullable) device [B][n], s_out device [B].
+ *   s_out[b] = max(quantile(|x_b|, ratio), max_val);  out = clamp(x, symmetric ? -s_b : 0, s_b) / s_b.   1 <= n < 2^31; launches on the current device. */
+DDIF_API int ddif_dynamic_threshold(const float* x, int B, int64_t n, float ratio, float max_val, int symmetric, float* out, float* s_out, void* stream);
+
 /* Per-sample rows of p_losses beyond sqrt_ac / sqrt_1mac (B floats each, HOST or DEVICE like those):
  *   recon_xt, recon_out: x0 = recon_xt[b] * x_t - recon_out[b] * prediction (:708-713, :724, :735), the schedule pair of ddif_pred_tables gathered at t;
  *     required unless the plan predicts x_start;

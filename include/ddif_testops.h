@@ -109,6 +109,11 @@ DDIF_API int ddif_q_sample(const float* x0, const float* noise, const float* a, 
 /* F.l1_loss(pred, target), mean reduction: out = one device float */
 DDIF_API int ddif_l1_loss_fwd(const float* pred, const float* target, int64_t n, float* out, void* stream);
 
+/* ---- the order statistics behind ddif_dynamic_threshold (csrc/kernels_quantile.h) ------------------------------------------
+ * x device [B][n]; s_out device [B] = the interpolated quantile of |x_b| (max_val = 0); stats device [B][2] = the two order statistics of |x_b| it
+ * interpolates between, rank floor(r) and ceil(r) of r = fp32(ratio) * fp32(n - 1): what torch.sort(|x_b|) holds at those indices, bit for bit. */
+DDIF_API int ddif_quantile_abs_stats(const float* x, int B, int64_t n, float ratio, float* s_out, float* stats, void* stream);
+
 /* ---- stage taps of an INFERENCE plan ----------------------------------------------------------------------------------------
  * The fused inference kernels (attn_block_kernel, self_attn_mfma_kernel, linattn_fused_kernel, linattn8_fused_kernel) are reachable through a plan only, and
  * an end-to-end comparison hardly sees them: GroupNorms and ~30 layers behind the bottleneck damp a wholly wrong attention below the forward tolerance

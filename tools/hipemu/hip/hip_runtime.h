@@ -186,6 +186,10 @@ static inline hipemu_f32x4 hipemu_mfma_16x16x4(float a, float b, hipemu_f32x4 c)
     return d;
 }
 
+// ---- integer atomics (LDS histograms of kernels_quantile.h).  The fibers of a workgroup share one OS thread and switch only at rendezvous points, so a
+// plain read-modify-write would do for LDS; the builtin also covers global memory, where workgroups run on different OS threads.
+static inline unsigned atomicAdd(unsigned* p, unsigned v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+
 // ---- math the kernels use ------------------------------------------------------------------------------
 static inline float rsqrtf(float x) { return 1.0f / sqrtf(x); }
 static inline float __frcp_rn(float x) { return 1.0f / x; }

@@ -8,6 +8,8 @@ written into the repository.
     python tools/make_golden.py --only ddpmbig,dpmbig,ddpmfull     (round 6: the config-exact cases; not part of the default set)
     python tools/make_golden.py --only objective                   (pred_mode noise / pred_v, l2, p2 weighting: tests/golden_cases_objective.py;
                                                                     each output also from an fp64 run of the reference; not part of the default set)
+    python tools/make_golden.py --only dynthresh                   (clamp_type="dynamic" / correcting_x0_fn="dynamic_thresholding": tests/golden_cases_dynthresh.py;
+                                                                    fp32 + fp64 as above, plus the reference's quantile per (step, sample); not part of the default set)
 """
 import argparse
 import json
@@ -281,6 +283,88 @@ def make_objective(UNetSR3, D, S, net_for):
     assert not too_noisy, f"the reference's own fp32-fp64 gap exceeds a tenth of the tolerance: change these cases: {too_noisy}"
 
 
+def make_dynthresh(UNetSR3, D, S, net_for):
+    """Dynamic thresholding (tests/golden_cases_dynthresh.py).  As make_objective: the reference as it is (fp32: the expected output) and its fp64 twin with the
+    same fp32 random draws; `quant` = what torch.quantile returned inside the fp32 run's dynamic_thresholding_fn, per (step, sample), in execution order."""
+    import copy
+
+    import golden_cases_dynthresh as gd
+
+    nets64 = {}
+
+    def net64_for(ds):
+        if ds not in nets64:
+            n = copy.deepcopy(net_for(ds)).double()
+            fwd = n.forward
+            n.forward = lambda x, t, cond=None, self_cond=None: fwd(x.double(), t, None if cond is None else cond.double(), None if self_cond is None else self_cond.double())
+            n.noise_level_mlp[0].register_forward_hook(lambda m, i, o: o.double())
+            nets64[ds] = n
+        return nets64[ds]
+
+    def diffusion(ds, T, size, pred_mode, f64, schedule=None, clamp_type="dynamic"):
+        net = net64_for(ds) if f64 else net_for(ds)
+        d = D.GaussianDiffusion(net, image_size=size, channels=gc.DATASETS[ds][0], pred_mode=pred_mode, loss_type="l2", device="cpu", clamp_range=(0, 1),
+                                clamp_type=clamp_type)
+        d.set_new_noise_schedule(betas=D.make_beta_schedule(**(schedule or dict(schedule="cosine", n_timestep=T, cosine_s=8e-3))))
+        return d.double() if f64 else d
+
+    def record(obj, quant):
+        """Wrap obj.dynamic_thresholding_fn (an instance attribute shadows the method; DPM_Solver stored the bound method already, so patch that slot too)."""
+        orig = obj.dynamic_thresholding_fn
+
+        def wrapped(x0, t):
+            quant.append(torch.quantile(torch.abs(x0).reshape((x0.shape[0], -1)), obj.dynamic_thresholding_ratio, dim=1).detach().clone())
+            return orig(x0, t)
+        obj.dynamic_thresholding_fn = wrapped
+        if getattr(obj, "correcting_x0_fn", None) is not None:
+            obj.correcting_x0_fn = wrapped
+
+    too_noisy, idle = [], []
+
+    def finish(cid, run, max_val, expect_active, tol_of, cond):
+        q32, q64 = [], []
+        out, out64 = run(False, q32), run(True, q64)
+        gap = float((out.double() - out64).abs().max())
+        tol = tol_of(out)
+        quant = torch.stack(q32).float()
+        frac = gd.active_fraction(quant.numpy(), max_val)
+        print(f"  {cid}: fp32-fp64 gap {gap:.2e}, max|golden| {float(out.abs().max()):.3g}, tolerance {tol:.2e} -> gap / tolerance = {gap / tol:.3f}; quantile "
+              f"{float(quant.min()):.4g} .. {float(quant.max()):.4g}, above max_val {max_val} in {int(round(frac * quant.numel()))} of {quant.numel()} (step, sample) pairs")
+        if gap > 0.1 * tol:
+            too_noisy.append(cid)
+        if expect_active and frac < 0.5:
+            idle.append(cid)
+        save(cid, out=out, out_f64=out64, gap=gap, quant=quant, max_val=max_val, cond_chk=chk(cond))
+
+    for cid, ds, B, H, W, T, pm, seed, expect_active in gd.DDPM_CASES:
+        cond = gc.tiles_for(ds, B, H, W, seed=seed)["cond"]
+
+        def run(f64, quant):
+            d = diffusion(ds, T, H, pm, f64)  # (before seeding: building a net draws from the generator)
+            record(d, quant)
+            torch.manual_seed(seed)
+            return d(cond.double() if f64 else cond, mode="ddpm_sample")
+        finish(cid, run, 1.0, expect_active, lambda out: 1e-4, cond)
+
+    for cid, ds, H, W, T, steps, order, mt, seed, kw in gd.DPM_CASES:
+        C = gc.DATASETS[ds][0]
+        cond = gc.tiles_for(ds, 1, H, W, seed=seed)["cond"]
+        xT = torch.randn(1, C, H, W, generator=torch.Generator().manual_seed(seed))
+
+        def run(f64, quant):
+            d = diffusion(ds, T, H, gd.PRED_OF_MODEL_TYPE[mt], f64, schedule=gd.dpm_schedule(mt, T), clamp_type="abs")
+            cnd, x = (cond.double(), xT.double()) if f64 else (cond, xT)
+            ns = S.NoiseScheduleVP("discrete", betas=d.betas.float())  # the schedule scalars stay in the solver's own fp32 in both runs, as in make_objective
+            fn = S.model_wrapper(d.model, ns, model_type=mt, guidance_type="classifier-free", guidance_scale=1.0, condition=cnd)
+            slv = S.DPM_Solver(fn, ns, algorithm_type="dpmsolver++", correcting_x0_fn="dynamic_thresholding", **kw)
+            record(slv, quant)
+            with torch.no_grad():
+                return slv.sample(x, steps=steps, order=order, skip_type="time_uniform", method="multistep")
+        finish(cid, run, float(kw["thresholding_max_val"]), True, lambda out: 1e-4 * max(1.0, float(out.abs().max())), cond)
+    assert not too_noisy, f"the reference's own fp32-fp64 gap exceeds a tenth of the tolerance: change these cases: {too_noisy}"
+    assert not idle, f"thresholding is active in less than half of the (step, sample) pairs: change these cases: {idle}"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="manifest,fwd,fwdbig,trunc,dpmskip,trainfwd,traingrad,sched,ddpm,ddim,dpm,loss,psnr")
@@ -535,6 +619,8 @@ def main():
 
     if "objective" in only:
         make_objective(UNetSR3, D, S, net_for)
+    if "dynthresh" in only:
+        make_dynthresh(UNetSR3, D, S, net_for)
 
     if "psnr" in only:
         import importlib.util
