@@ -1725,7 +1725,13 @@ int Plan::train_step(const float* x0, const float* noise, const float* a_h, cons
 // ---- objective (include/ddif.h ddif_plan_set_objective)
 int Plan::set_objective(int pred, int loss) {
     if (pred != DDIF_PRED_X_START && pred != DDIF_PRED_NOISE && pred != DDIF_PRED_V) return fail(DDIF_ERR_INVALID, "ddif_plan_set_objective: pred_mode %d (0 x_start, 1 noise, 2 pred_v)", pred);
-    if (loss != DDIF_LOSS_L1 && loss != DDIF_LOSS_L2) return fail(DDIF_ERR_INVALID, "ddif_plan_set_objective: loss_type %d (0 l1, 1 l2)", loss);
+    if (loss != DDIF_LOSS_L1 && loss != DDIF_LOSS_L2 && loss != DDIF_LOSS_L1SSIM) return fail(DDIF_ERR_INVALID, "ddif_plan_set_objective: loss_type %d (0 l1, 1 l2, 2 l1ssim)", loss);
+    if (loss == DDIF_LOSS_L1SSIM && train_mode && !ssim_maps) {  // the scratch of the SSIM tail (ddif_ssimloss.cpp): only a plan that trains under this loss pays for it
+        if (int e = tk::ssimloss_check("ddif_plan_set_objective (l1ssim)", B, C, H, W)) return e;
+        if (!ssim_part)
+            if (int e = dalloc(&ssim_part, 2 * tk::ssimloss_workgroups(B, C, H, W))) return e;
+        if (int e = dalloc(&ssim_maps, (size_t)3 * B * H * W * C)) return e;
+    }
     if ((pred != DDIF_PRED_X_START) != (pred_mode != DDIF_PRED_X_START)) drop_graphs();  // the captured step holds the other final-conv instantiation
     pred_mode = pred;
     loss_type = loss;

@@ -116,6 +116,11 @@ void gn_bwd_cat(hipStream_t s, const float* x0, int c0, const float* x1, int c1,
 void linear_bwd(hipStream_t s, const float* x, const float* w, const float* dy, int B, int nin, int nout, float* dx, float* dw, float* db);
 void l1_fwd(hipStream_t s, const float* pred, const float* target, size_t n, float* out);
 void l1_bwd(hipStream_t s, const float* pred, const float* target, size_t n, float upstream, float* dpred);
+// kernels_ssimloss.h  (ddif_ssimloss.cpp): the three launches of the HybridL1SSIM loss -- statistics + maps, final scalar (d_loss[0] loss, d_loss[1] p2 factor), gradient
+size_t ssimloss_workgroups(int B, int C, int H, int W);  // `part` holds two doubles per workgroup
+int ssimloss_check(const char* who, int B, int C, int H, int W);
+void ssimloss_tail(hipStream_t s, const float* img1, const float* img2, int B, int C, int H, int W, bool nhwc, float w_l1, float w_ssim, float upstream, const float* p2w,
+                   float* maps, double* part, float* d_loss, float* d_img2);  // d_img2 null: the value only (maps unused)
 // kernels_misc.h  (ddif_plan.cpp)
 void dw3x3_plain(hipStream_t s, const float* in, int C, int B, int H, int W, const float* w9c, float* out, bool flip = false);  // depthwise conv, weights [9][C]
 }  // namespace tk
@@ -198,6 +203,10 @@ struct Plan {
     // objective (ddif_plan_set_objective; sticky): what the network output means and which loss the training step takes.  Defaults = the engine's.
     int pred_mode = DDIF_PRED_X_START, loss_type = DDIF_LOSS_L1;
     int set_objective(int pred, int loss);
+    // DDIF_LOSS_L1SSIM: HybridL1SSIM's weighted_r (utils/loss_utils.py:74) and the scratch of its tail, allocated when a train-mode plan first takes that loss
+    float w_l1 = 1.0f, w_ssim = 0.1f;
+    float* ssim_maps = nullptr;         // [3][B H W C]
+    double* ssim_part = nullptr;        // [tk::ssimloss_workgroups][2]
     // dynamic thresholding (ddif_plan_set_threshold; sticky): 0 off, 1 the DDPM form (clamp(v, 0, s) / s around lms), 2 the solver form (clamp(x0, -s, s) / s)
     int thr_mode = DDIF_THRESHOLD_OFF;
     float thr_ratio = 0.f, thr_max = 1.f;

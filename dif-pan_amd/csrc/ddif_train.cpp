@@ -744,6 +744,10 @@ int Plan::build_backward() {
 int Plan::train_backward(const float* target_nhwc, float upstream, float* loss_dev, hipStream_t s, const float* p2w) {
     const size_t n = (size_t)B * H * W * C;
     const int nblk = 256;
+    if (loss_type == DDIF_LOSS_L1SSIM) {  // HybridL1SSIM(target, net_out) (:194-195): statistics + maps, final scalar with the p2 factor, gradient (ddif_ssimloss.cpp)
+        if (!ssim_maps || !ssim_part) return fail(DDIF_ERR_STATE, "training step: the l1ssim scratch is missing (ddif_plan_set_objective allocates it)");
+        tk::ssimloss_tail(s, target_nhwc, net_out.p, B, C, H, W, true, w_l1, w_ssim, upstream, p2w, ssim_maps, ssim_part, d_loss, d_net_out);
+    } else
     if (loss_type == DDIF_LOSS_L1 && !p2w) {  // the engine's configuration: the launches it always had
         hipLaunchKernelGGL(l1_partial_kernel, dim3(nblk), dim3(256), 256 * sizeof(double), s, (const float*)net_out.p, target_nhwc, n, ts->spart);
         hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(64), 0, s, (const double*)ts->spart, nblk, n, d_loss);

@@ -8,8 +8,8 @@ hand-written gfx950 kernels on the current stream.
 
 Implemented: conditional models, pred_mode "x_start" / "noise" / "pred_v" (samplers, p_losses, the native training step),
 clamp_type="abs" and "dynamic" (Imagen's dynamic thresholding in the DDPM loop: an exact per-sample quantile kernel in front of the update,
-`ddif_plan_set_threshold`), loss "l1" / "l2" (value and backward pass), p2 loss weighting.  Still refused (DdifError, no fallback):
-unconditional models, loss_type="l1ssim", get_interm_fm.
+`ddif_plan_set_threshold`), loss "l1" / "l2" / "l1ssim" (value and backward pass; `HybridL1SSIM` below is the reference's utils/loss_utils.py class over
+`ddif_l1ssim_loss`), p2 loss weighting.  Still refused (DdifError, no fallback): unconditional models, get_interm_fm.
 """
 from __future__ import annotations
 
@@ -22,6 +22,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from .. import runtime as _rt
 from ..runtime import DdifError
 
 
@@ -62,6 +63,40 @@ def default(val, d):
 def extract(a, t, x_shape):
     b = t.shape[0]
     return a.gather(-1, t).reshape(b, *((1,) * (len(x_shape) - 1)))
+
+
+class _L1SSIMFn(torch.autograd.Function):
+    """HybridL1SSIM's value and gradients from `ddif_l1ssim_loss` (csrc/kernels_ssimloss.h).  The forward call computes the value only; backward() runs the
+    kernels again with the gradient launch, once per argument that requires grad -- with the arguments swapped for the first (the loss is symmetric)."""
+
+    @staticmethod
+    def forward(ctx, img1, img2, w_l1, w_ssim):
+        ctx.save_for_backward(img1, img2)
+        ctx.weights = (w_l1, w_ssim)
+        return _rt.l1ssim_loss(img1, img2, ctx.weights)
+
+    @staticmethod
+    def backward(ctx, gloss):
+        img1, img2 = ctx.saved_tensors
+        up = float(gloss)
+        g1 = _rt.l1ssim_loss(img2, img1, ctx.weights, grad=True, upstream=up)[1] if ctx.needs_input_grad[0] else None
+        g2 = _rt.l1ssim_loss(img1, img2, ctx.weights, grad=True, upstream=up)[1] if ctx.needs_input_grad[1] else None
+        return g1, g2, None, None
+
+
+class HybridL1SSIM(nn.Module):
+    """The reference's utils/loss_utils.py:73-83 with its constructor and call signature: L1Loss * weighted_r[0] + SSIMLoss * weighted_r[1], SSIMLoss = 1 - mean of
+    the SSIM map under an 11 x 11 Gaussian window (sigma 1.5, zero padding 5).  `channel` is kept for the signature: as in the reference (:131-143) the window
+    follows the input's channel count.  No torch compute: value and gradients come from the HIP kernels."""
+
+    def __init__(self, channel=31, weighted_r=(1.0, 0.1)):
+        super().__init__()
+        assert len(weighted_r) == 2
+        self.channel = channel
+        self.weighted_r = (float(weighted_r[0]), float(weighted_r[1]))
+
+    def forward(self, pred, gt):
+        return _L1SSIMFn.apply(pred, gt, *self.weighted_r)
 
 
 class _NativeTrainFn(torch.autograd.Function):
@@ -133,8 +168,8 @@ class GaussianDiffusion(nn.Module):
             self.loss_func = nn.L1Loss().to(device)
         elif self.loss_type == "l2":
             self.loss_func = nn.MSELoss().to(device)
-        else:
-            raise DdifError("loss_type='l1ssim' is not implemented by the HIP path (the engine uses 'l1')")
+        else:  # "l1ssim" (:194-195)
+            self.loss_func = HybridL1SSIM(channel=self.channels).to(device)
 
     def set_new_noise_schedule(self, schedule_opt=None, device="cpu", *, betas=None):
         to_torch = partial(torch.tensor, dtype=torch.float32, device=device)

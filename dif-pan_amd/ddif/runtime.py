@@ -60,7 +60,7 @@ class ObjectiveRows(C.Structure):
 
 
 PRED_MODES = {"x_start": 0, "noise": 1, "pred_v": 2, "v": 2}  # GaussianDiffusion's names + model_wrapper's "v" (include/ddif.h DDIF_PRED_*)
-LOSS_TYPES = {"l1": 0, "l2": 1}
+LOSS_TYPES = {"l1": 0, "l2": 1, "l1ssim": 2}  # include/ddif.h DDIF_LOSS_*
 THRESHOLD_MODES = {"off": 0, "ddpm": 1, "solver": 2}  # include/ddif.h DDIF_THRESHOLD_*
 
 
@@ -123,6 +123,7 @@ class _Lib:
         d.ddif_plan_set_threshold.argtypes = [vp, i32, f32, f32]
         d.ddif_plan_get_threshold.argtypes = [vp, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32)]
         d.ddif_dynamic_threshold.argtypes = [vp, i32, C.c_int64, f32, f32, i32, vp, vp, vp]
+        d.ddif_l1ssim_loss.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp]
         d.ddif_plan_sample_ddpm_ex.argtypes = [vp, C.POINTER(DdpmTables), C.POINTER(PredTables), vp, vp, u64, u64, f32, f32, i32, vp, vp]
         d.ddif_plan_sample_ddim_ex.argtypes = [vp, C.POINTER(DdimTables), C.POINTER(PredTables), vp, vp, u64, u64, f32, f32, i32, vp, vp]
         d.ddif_plan_q_sample_forward_ex.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(ObjectiveRows), vp, vp, vp]
@@ -427,7 +428,7 @@ class PlanHandle:
 
     def set_objective(self, pred_mode: str = "x_start", loss_type: str = "l1"):
         """What the network output means to the samplers / p_losses and which loss the training step takes (include/ddif.h
-        ddif_plan_set_objective; sticky).  pred_mode: "x_start" | "noise" | "pred_v" (alias "v"), loss_type: "l1" | "l2"."""
+        ddif_plan_set_objective; sticky).  pred_mode: "x_start" | "noise" | "pred_v" (alias "v"), loss_type: "l1" | "l2" | "l1ssim"."""
         if pred_mode not in PRED_MODES or loss_type not in LOSS_TYPES:
             raise DdifError(f"objective ({pred_mode!r}, {loss_type!r}): pred_mode in {sorted(PRED_MODES)}, loss_type in {sorted(LOSS_TYPES)}")
         obj = ("pred_v" if pred_mode == "v" else pred_mode, loss_type)
@@ -439,7 +440,7 @@ class PlanHandle:
         """(pred_mode, loss_type) as the LIBRARY holds them for this plan (include/ddif.h ddif_plan_get_objective)."""
         a, b = C.c_int(), C.c_int()
         self.lib.check(self.lib.dll.ddif_plan_get_objective(self.h, C.byref(a), C.byref(b)), "ddif_plan_get_objective")
-        return ({0: "x_start", 1: "noise", 2: "pred_v"}[a.value], {0: "l1", 1: "l2"}[b.value])
+        return ({0: "x_start", 1: "noise", 2: "pred_v"}[a.value], {v: k for k, v in LOSS_TYPES.items()}[b.value])
 
     def _objective_rows(self, rows, device):
         """ObjectiveRows from (recon_xt, recon_out, p2_weight) tensors (each nullable); returns (struct or None, keep-alive list)."""
@@ -812,6 +813,28 @@ def dynamic_threshold(x0: torch.Tensor, ratio: float, max_val: float, symmetric:
     lib.check(lib.dll.ddif_dynamic_threshold(_ptr(x), B, x.numel() // B, float(ratio), float(max_val), 1 if symmetric else 0, _ptr(out), _ptr(s),
                                              _stream(lib, x.device)), "ddif_dynamic_threshold")
     return out, s
+
+
+def l1ssim_loss(img1: torch.Tensor, img2: torch.Tensor, weights=(1.0, 0.1), *, grad: bool = False, upstream: float = 1.0, nhwc: bool = False):
+    """The reference's HybridL1SSIM(weighted_r=weights)(img1, img2) (utils/loss_utils.py:73-83; include/ddif.h ddif_l1ssim_loss): mean L1 * weights[0] +
+    (1 - mean SSIM map) * weights[1], 11 x 11 Gaussian window (sigma 1.5), zero padding.  (B, C, H, W) tensors, or (B, H, W, C) with nhwc=True.  Returns the
+    loss (a 0-d tensor); with grad=True returns (loss, upstream * d loss / d img2) -- the loss is symmetric, so swap the arguments for the other gradient."""
+    lib = get_lib()
+    _check_tensor(lib, img1, "img1")
+    _check_tensor(lib, img2, "img2")
+    _check_current_device(img1, "img1")
+    if img1.dim() != 4 or img1.numel() == 0:
+        raise DdifError(f"img1: expected a non-empty 4-d tensor, got shape {tuple(img1.shape)}")
+    _check_shape(img2, "img2", tuple(img1.shape))
+    if len(weights) != 2:
+        raise DdifError(f"weights: expected (w_l1, w_ssim), got {weights!r}")
+    a, b = img1.contiguous(), img2.contiguous()
+    B, Cc, H, W = (a.shape[0], a.shape[3], a.shape[1], a.shape[2]) if nhwc else tuple(a.shape)
+    loss = torch.empty((), dtype=torch.float32, device=a.device)
+    d = torch.empty_like(b) if grad else None
+    lib.check(lib.dll.ddif_l1ssim_loss(_ptr(a), _ptr(b), B, Cc, H, W, 1 if nhwc else 0, float(weights[0]), float(weights[1]), float(upstream), _ptr(loss),
+                                       None if d is None else _ptr(d), _stream(lib, a.device)), "ddif_l1ssim_loss")
+    return (loss, d) if grad else loss
 
 
 def metrics(gt: torch.Tensor, pred: torch.Tensor, ergas_ratio: float = 4.0) -> torch.Tensor:

@@ -173,8 +173,21 @@ DDIF_API int ddif_plan_q_sample_forward(ddif_plan_t plan, const float* x0, const
 #define DDIF_PRED_V 2
 #define DDIF_LOSS_L1 0   /* nn.L1Loss  (:152-153) */
 #define DDIF_LOSS_L2 1   /* nn.MSELoss (:154-155) */
+#define DDIF_LOSS_L1SSIM 2 /* HybridL1SSIM(channel=channels), weighted_r = (1.0, 0.1) (:194-195; utils/loss_utils.py:73-83); any pred_mode, with or without p2_weight */
 DDIF_API int ddif_plan_set_objective(ddif_plan_t plan, int pred_mode, int loss_type);
 DDIF_API int ddif_plan_get_objective(ddif_plan_t plan, int* pred_mode, int* loss_type);
+
+/* HybridL1SSIM on plain tensors (utils/loss_utils.py:73-83 over LossWarpper :98-115, SSIMLoss :118-147 and _ssim :30-59), the kernels of the training step's
+ * DDIF_LOSS_L1SSIM tail (csrc/kernels_ssimloss.h):
+ *   loss = 0.0 + mean|img1 - img2| * w_l1 + (1 - mean(ssim_map(img1, img2))) * w_ssim                                   (fp32 scalars, this order)
+ *   ssim_map = ((2 mu1 mu2 + C1)(2 s12 + C2)) / ((mu1^2 + mu2^2 + C1)(s11 + s22 + C2)),  C1 = 0.01^2, C2 = 0.03^2       (data_range is unused, as there)
+ *   mu = W*img, s11 = W*(img1 img1) - mu1^2, s22 = W*(img2 img2) - mu2^2, s12 = W*(img1 img2) - mu1 mu2
+ * W* = the depthwise 11 x 11 Gaussian window (sigma 1.5; gaussian / create_window :11-27: fp32 values divided by their fp32 sum) with ZERO padding 5; the means
+ * run over all B*C*H*W values.  img1, img2, d_img2: device tensors [B][C][H][W] (nhwc == 0) or [B][H][W][C] (nhwc != 0); any B, C, H, W >= 1.
+ * loss_out: one float, host or device.  d_img2 (nullable): upstream * d loss / d img2.  The loss is symmetric in its arguments: the gradient with respect to
+ * img1 is this call with the two swapped.  Bitwise reproducible (no atomics).  Allocates its scratch per call and synchronises the stream before returning. */
+DDIF_API int ddif_l1ssim_loss(const float* img1, const float* img2, int B, int C, int H, int W, int nhwc, float w_l1, float w_ssim, float upstream, float* loss_out,
+                              float* d_img2, void* stream);
 
 /* The per-step coefficients of x0 = coef_xt * x_t - coef_out * out (HOST arrays of n_steps floats in execution order, gathered from the schedule
  * buffers like the other tables): (sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod) for noise, (sqrt_alphas_cumprod,

@@ -10,6 +10,8 @@ written into the repository.
                                                                     each output also from an fp64 run of the reference; not part of the default set)
     python tools/make_golden.py --only dynthresh                   (clamp_type="dynamic" / correcting_x0_fn="dynamic_thresholding": tests/golden_cases_dynthresh.py;
                                                                     fp32 + fp64 as above, plus the reference's quantile per (step, sample); not part of the default set)
+    python tools/make_golden.py --only l1ssim                      (loss_type="l1ssim": the HybridL1SSIM operator, p_losses and its backward pass:
+                                                                    tests/golden_cases_l1ssim.py; fp32 + fp64 as above; not part of the default set)
 """
 import argparse
 import json
@@ -365,6 +367,166 @@ def make_dynthresh(UNetSR3, D, S, net_for):
     assert not idle, f"thresholding is active in less than half of the (step, sample) pairs: change these cases: {idle}"
 
 
+def make_l1ssim(UNetSR3, D, S, net_for):
+    """loss_type="l1ssim" (tests/golden_cases_l1ssim.py).  As make_objective, whose twin construction, pinning of t and mask capture this repeats for the one loss:
+    the reference as it is (fp32: the expected value) and its fp64 twin with the same fp32 random draws, `<key>_f64` and `gap::<key>` next to every value.
+    HybridL1SSIM keeps its window as a plain attribute and rebuilds it `type_as` the input (utils/loss_utils.py:133-142), so the twin filters with the SAME
+    fp32-rounded weights in double arithmetic."""
+    import copy
+
+    import golden_cases_l1ssim as gl
+
+    nets64 = {}
+
+    def net64_for(ds):
+        if ds not in nets64:
+            n = copy.deepcopy(net_for(ds)).double()
+            fwd = n.forward
+            n.forward = lambda x, t, cond=None, self_cond=None: fwd(x.double(), t, None if cond is None else cond.double(), None if self_cond is None else self_cond.double())
+            n.noise_level_mlp[0].register_forward_hook(lambda m, i, o: o.double())
+            nets64[ds] = n
+        return nets64[ds]
+
+    def diffusion(ds, T, size, pred_mode, gamma, f64):
+        net = net64_for(ds) if f64 else net_for(ds)
+        d = D.GaussianDiffusion(net, image_size=size, channels=gc.DATASETS[ds][0], pred_mode=pred_mode, loss_type="l1ssim", device="cpu", clamp_range=(0, 1),
+                                p2_loss_weight_gamma=gamma)
+        d.set_new_noise_schedule(betas=D.make_beta_schedule(schedule="cosine", n_timestep=T, cosine_s=8e-3))
+        assert isinstance(d.loss_func, D.HybridL1SSIM) and tuple(d.loss_func.loss.weighted_ratio) == gl.WEIGHTS
+        return d.double() if f64 else d
+
+    too_noisy = []
+
+    def report(cid, gap, tol):
+        print(f"  {cid}: fp32-fp64 gap {gap:.2e}, tolerance {tol:.2e} -> gap / tolerance = {gap / tol:.3f}")
+        if gap > 0.1 * tol:
+            too_noisy.append(cid)
+
+    class Pin:
+        def __init__(self, tt, sc_branch):
+            self.tt, self.sc = tt, sc_branch
+
+        def __enter__(self):
+            self.ri, self.rr = torch.randint, random.random
+            D.torch.randint = lambda *a, **k: self.tt
+            D.random.random = (lambda: 0.0) if self.sc else (lambda: 1.0)
+
+        def __exit__(self, *a):
+            D.torch.randint, D.random.random = self.ri, self.rr
+
+    # ---- the operator: HybridL1SSIM(channel=C)(x, y) and autograd's gradients with respect to both arguments
+    for case in gl.OP_CASES:
+        cid, C = case[0], case[2]
+        x, y = gl.op_inputs(case)
+        res = {}
+        for f64 in (False, True):
+            a, b = (v.double() if f64 else v.clone() for v in (x, y))
+            a.requires_grad_(True), b.requires_grad_(True)
+            loss = D.HybridL1SSIM(channel=C)(a, b)
+            loss.backward()
+            res[f64] = (loss.detach().reshape(1), a.grad.detach(), b.grad.detach())
+        (l, g1, g2), (l64, g1_64, g2_64) = res[False], res[True]
+        gap_l = float((l.double() - l64).abs().max())
+        rel = lambda g, g64: float((g.double() - g64).abs().max()) / max(float(g64.abs().max()), 1e-5)
+        report(f"{cid} loss", gap_l, 1e-6)
+        report(f"{cid} d/d img1 (relative)", rel(g1, g1_64), 5e-5)
+        report(f"{cid} d/d img2 (relative)", rel(g2, g2_64), 5e-5)
+        save(cid, x=x, y=y, loss=l, loss_f64=l64, grad1=g1, grad1_f64=g1_64, grad2=g2, grad2_f64=g2_64,
+             **{"gap::loss": gap_l, "gap::grad1_rel": rel(g1, g1_64), "gap::grad2_rel": rel(g2, g2_64)})
+
+    # ---- p_losses in eval mode
+    for stem, ds, B, H, W, T, tvals, sc_branch, seed in gl.LOSS_CASES:
+        C = gc.DATASETS[ds][0]
+        tiles = gc.tiles_for(ds, B, H, W, seed=seed)
+        cond, res_ = tiles["cond"], tiles["gt"] - tiles["lms"]
+        noise = torch.randn(B, C, H, W, generator=torch.Generator().manual_seed(seed))
+        tt = torch.tensor(tvals, dtype=torch.long)
+        for pm in gl.PRED_MODES:
+            arrs = {}
+            for gamma in gl.P2_GAMMAS:
+                out = {}
+                for f64 in (False, True):
+                    d = diffusion(ds, T, H, pm, gamma, f64)
+                    cast = (lambda v: v.double()) if f64 else (lambda v: v)
+                    with Pin(tt, sc_branch), torch.no_grad():
+                        loss, recon = d(cast(res_), mode="train", noise=cast(noise), cond=cast(cond))
+                    out[f64] = (loss.reshape(1), recon)
+                k = gl.loss_key(gamma)
+                (loss, recon), (loss64, recon64) = out[False], out[True]
+                gl_, gr = float((loss.double() - loss64).abs().max()), float((recon.double() - recon64).abs().max())
+                report(f"{stem}_{pm} {k} loss", gl_, 1e-6)
+                report(f"{stem}_{pm} {k} recon", gr, 2e-5)
+                arrs.update({f"loss_{k}": loss, f"loss_{k}_f64": loss64, f"gap::loss_{k}": gl_, f"recon_{k}": recon, f"recon_{k}_f64": recon64, f"gap::recon_{k}": gr})
+            save(f"{stem}_{pm}", cond_chk=chk(cond), **arrs)
+
+    # ---- p_losses(...).backward() under .train(): the fp32 run captures the Dropout / DropPath masks, the fp64 run imposes them
+    for cid, ds, B, H, W, T, tvals, pm, gamma, seed in gl.GRAD_CASES:
+        C = gc.DATASETS[ds][0]
+        tiles = gc.tiles_for(ds, B, H, W, seed=seed)
+        cond, res_ = tiles["cond"], tiles["gt"] - tiles["lms"]
+        noise = torch.randn(B, C, H, W, generator=torch.Generator().manual_seed(seed))
+        tt = torch.tensor(tvals, dtype=torch.long)
+        drops, paths = [], []
+
+        def run(f64):
+            d = diffusion(ds, T, H, pm, gamma, f64)
+            net = d.model
+            hooks, k = [], [0, 0]
+            for m in net.modules():
+                if isinstance(m, nn.Dropout):
+                    if not f64:
+                        hooks.append(m.register_forward_hook(lambda mod, inp, out: drops.append(((out != 0) | (inp[0] == 0)).detach())))
+                    else:
+                        def imp(mod, inp, out):
+                            k[0] += 1
+                            return inp[0] * drops[k[0] - 1].double() / (1 - mod.p)
+                        hooks.append(m.register_forward_hook(imp))
+                elif type(m).__name__ == "DropPath":
+                    if not f64:
+                        hooks.append(m.register_forward_hook(lambda mod, inp, out: paths.append(((out.detach().flatten(1).abs().sum(1) != 0).float() / (1 - mod.drop_prob)))))
+                    else:
+                        def impp(mod, inp, out):
+                            k[1] += 1
+                            return inp[0] * paths[k[1] - 1].double().reshape(-1, 1, 1, 1)
+                        hooks.append(m.register_forward_hook(impp))
+            net.train()
+            for prm in net.parameters():
+                prm.requires_grad_(True)
+                prm.grad = None
+            torch.manual_seed(seed)
+            cast = (lambda v: v.double()) if f64 else (lambda v: v)
+            try:
+                with Pin(tt, False):
+                    loss, recon = d(cast(res_), mode="train", noise=cast(noise), cond=cast(cond))
+                loss.backward()
+            finally:
+                net.eval()
+                for hk in hooks:
+                    hk.remove()
+            names = [n for n, _ in net.named_parameters()]
+            norms = np.array([float(prm.grad.double().norm()) if prm.grad is not None else -1.0 for _, prm in net.named_parameters()], dtype=np.float64)
+            full = {"grad::" + n: prm.grad.detach().clone() for n, prm in net.named_parameters() if any(n == f or n.startswith(f) for f in gl.TRAIN_GRAD_FULL)}
+            for prm in net.parameters():
+                prm.grad = None
+                prm.requires_grad_(False)
+            return float(loss.detach()), recon.detach(), names, norms, full
+
+        loss, recon, names, norms, full = run(False)
+        loss64, recon64, _, norms64, full64 = run(True)
+        rel = float(np.max(np.abs(norms - norms64) / np.maximum(norms64, 1e-4)))
+        gfull = max(float((full[k].double() - full64[k]).abs().max()) / max(float(full64[k].abs().max()), 1e-5) for k in full)
+        grec = float((recon.double() - recon64).abs().max())
+        print(f"  {cid}: loss gap {abs(loss - loss64):.2e} (tolerance 1e-6), recon gap {grec:.2e} (tolerance 2e-5), worst relative grad-norm gap {rel:.2e} (tolerance 2e-4), "
+              f"worst relative full-gradient gap {gfull:.2e} (tolerance 5e-5)")
+        if not (abs(loss - loss64) <= 1e-7 and grec <= 2e-6 and rel <= 2e-5 and gfull <= 5e-6):
+            too_noisy.append(cid)
+        arrs = {f"drop_{k}": np.packbits(d_.numpy().reshape(-1)) for k, d_ in enumerate(drops)}
+        arrs.update({f"drop_{k}_shape": np.array(d_.shape) for k, d_ in enumerate(drops)})
+        save(cid, loss=loss, loss_f64=loss64, recon=recon, recon_f64=recon64, n_drop=len(drops), paths=torch.stack(paths), p_drop=0.2, names=np.array(names), grad_norms=norms,
+             grad_norms_f64=norms64, **{"gap::loss": abs(loss - loss64), "gap::recon": grec, "gap::grad_norms_rel": rel, "gap::grad_full_rel": gfull}, **arrs, **full)
+    assert not too_noisy, f"the reference's own fp32-fp64 gap exceeds a tenth of the tolerance: change the seed or the pinned t of these cases: {too_noisy}"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="manifest,fwd,fwdbig,trunc,dpmskip,trainfwd,traingrad,sched,ddpm,ddim,dpm,loss,psnr")
@@ -621,6 +783,8 @@ def main():
         make_objective(UNetSR3, D, S, net_for)
     if "dynthresh" in only:
         make_dynthresh(UNetSR3, D, S, net_for)
+    if "l1ssim" in only:
+        make_l1ssim(UNetSR3, D, S, net_for)
 
     if "psnr" in only:
         import importlib.util
