@@ -440,6 +440,12 @@ int Net::commit(hipStream_t stream) {
         if (wr) {
             vec_off[ci + ".attn_res.weight"] = b.add(wr->v.data(), wr->v.size());
             rec_copy(RF_COPY, ci + ".attn_res.weight", "", vec_off[ci + ".attn_res.weight"], wr->v.size());
+            // W_res alone as f16x2 planes for the fused linear-attention kernels (kernels_lafuse.h RF16; the layout of q.1's pack); absent when a weight is
+            // outside the scaled half range.  Inference only: no refresh recipe (merged_stale)
+            if (wr->shape.size() == 4 && wr->shape[1] % 32 == 0) {
+                const size_t off = pack_conv_f16(b, wr->v.data(), (int)wr->shape[0], (int)wr->shape[1], 1, 32);
+                if (off != (size_t)-1) vec_off[ci + ".attn_res.weight.f16"] = off;
+            }
         }
         if (wo && bo) {
             const int co = (int)wo->shape[0], fea = (int)wo->shape[1];

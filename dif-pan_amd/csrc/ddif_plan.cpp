@@ -1356,6 +1356,17 @@ struct PlanBuilder {
         a.bias = pm->bias;
         a.out = amix->p;
         a.dout = pm->cout;
+        {   // attn_res(xn) on f16x2 (three products, two operand planes) under the rule of attn_block's qkv: W_res has a half pack (|w| < 64, ddif_net.cpp) and the
+            // bound sqrt(N) max|gamma| + max|beta| of prenorm_x's output stays inside the scaled half range; otherwise, and under DDIF_LA_RES_F16=0, bf16x3 out of
+            // the per-sample [M_b | W_res] pack, whose size and layout do not depend on the choice
+            static const bool rf16 = env_flag("DDIF_LA_RES_F16", true);
+            const float* w16 = V(ci + ".attn_res.weight.f16");
+            auto ig = net.vec_absmax.find(D.pn_g), ib = net.vec_absmax.find(D.pn_b);
+            const bool okr = ig != net.vec_absmax.end() && ib != net.vec_absmax.end() &&
+                             std::sqrt((double)fea * Hl * Wl) * ig->second + ib->second < DDIF_F16_AMAX;
+            a.wres16 = (rf16 && w16 && okr) ? w16 : nullptr;
+            a.nchr = fea / 32;
+        }
         // four-wave workgroups of 128 pixels instead of eight-wave ones of 256 when the latter would not fill the CUs (round 6; same results either way:
         // kernels_lafuse.h).  DDIF_LA_NW = 8 / 4 forces one form (tests/test_env_switches.py).
         int la_nw = 8;
@@ -1364,26 +1375,36 @@ struct PlanBuilder {
             const long wg8 = (long)B * ((Wl + lafuse_strip(Hl, 8) - 1) / lafuse_strip(Hl, 8));
             la_nw = nw_env == 4 || nw_env == 8 ? nw_env : (wg8 < num_cus() ? 4 : 8);
         }
-        if (!p.dry) DDIF_TRY(la8 ? lafuse8_launch(a, 1, nullptr, true) : lafuse_launch(a, 1, nullptr, true, la_nw));
-        const int nstrips = la8 ? 2 : (Wl + lafuse_strip(Hl, la_nw) - 1) / lafuse_strip(Hl, la_nw);
+        // ... and 64-pixel workgroups whose four waves split the output channels (kernels_lafuse.h CS = 2) when twice the four-wave grid still fits the CUs (the 16 x 16
+        // level up to B = 64 on 256 CUs); never where the four-wave grid already fills them.  Bit-identical either way; DDIF_LA_CSPLIT=0 keeps the four-wave form
+        int la_cs = 1;
+        if (!la8 && la_nw == 4) {
+            static const bool cs_env = env_flag("DDIF_LA_CSPLIT", true);
+            const long wg4 = (long)B * ((Wl + lafuse_strip(Hl, 4) - 1) / lafuse_strip(Hl, 4));
+            if (cs_env && lafuse_csplit_supported(Hl, fea, pm->cout) && 2 * wg4 <= num_cus()) la_cs = 2;
+        }
+        if (!p.dry) DDIF_TRY(la8 ? lafuse8_launch(a, 1, nullptr, true) : lafuse_launch(a, 1, nullptr, true, la_nw, la_cs));
+        const int nstrips = la8 ? 2 : (Wl + lafuse_strip(Hl, la_nw, la_cs) - 1) / lafuse_strip(Hl, la_nw, la_cs);
         long cap = num_cus();
         if (g_debug_grid_cap > 0 && g_debug_grid_cap < cap) cap = g_debug_grid_cap;
         Op op;
         op.name = la8 ? "linattn8_fused" : "linattn_fused";
         {
             char lb[160];
-            snprintf(lb, sizeof lb, "linattn_fused GN+dw3x3+q.1+softmax_H+attn_out+res %d+%d->%d @%dx%d", cur.C, skip.C, pm->cout, Hl, Wl);
+            snprintf(lb, sizeof lb, "linattn_fused GN+dw3x3+q.1+softmax_H+attn_out+res(%s) %d+%d->%d @%dx%d", a.wres16 ? "f16x2" : "bf16x3", cur.C, skip.C, pm->cout, Hl, Wl);
             op.label = lb;
         }
+        if (getenv("DDIF_DUMP_PLAN"))  // (its own prefix: the `[ddif plan]` lines are the convs of add_conv, tools/plan_signature.py)
+            fprintf(stderr, "[ddif la] %-34s res=%s nw=%d csplit=%d\n", ci.c_str(), a.wres16 ? "f16x2" : "bf16x3", la_nw, la_cs);
         op.flop = 2.0 * B * Hl * Wl * ((double)fea * fea + 9.0 * fea + 2.0 * fea * pm->cout);
         op.bytes = 4.0 * B * Hl * Wl * ((double)fea + pm->cout);
         op.cls = cls_small(Hl * Wl, 1);
-        // q.1 on f16x2 (x3), attn_out / attn_res on bf16x3 (x6): weight of the sum
-        op.mfma_w = (3.0 * fea * fea + 6.0 * 2.0 * fea * pm->cout) / ((double)fea * fea + 9.0 * fea + 2.0 * fea * pm->cout);
-        op.run = [a, nstrips, cap, la8, la_nw](hipStream_t st, const StepCtx&) {
+        // q.1 on f16x2 (x3), attn_out on bf16x3 (x6), attn_res on either: weight of the sum
+        op.mfma_w = (3.0 * fea * fea + (6.0 + (a.wres16 ? 3.0 : 6.0)) * fea * pm->cout) / ((double)fea * fea + 9.0 * fea + 2.0 * fea * pm->cout);
+        op.run = [a, nstrips, cap, la8, la_nw, la_cs](hipStream_t st, const StepCtx&) {
             const long nw = (long)a.B * nstrips;
             if (la8) (void)lafuse8_launch(a, (int)(nw < cap ? nw : cap), st, false);
-            else (void)lafuse_launch(a, (int)(nw < cap ? nw : cap), st, false, la_nw);
+            else (void)lafuse_launch(a, (int)(nw < cap ? nw : cap), st, false, la_nw, la_cs);
         };
         step.push_back(std::move(op));
         *fused = true;

@@ -14,6 +14,7 @@
 //   per 16-channel chunk:  raw halo tile (prefetched one chunk ahead, registers) -> GroupNorm -> Hs (fp32, LDS) | barrier |
 //                          depthwise 3x3 -> dwq as two half planes (f16x2, ddif_dev.h), centre of Hs -> xn as three bf16 planes | barrier |
 //                          acc_q += W_q[chunk] dwq  (f16x2, 3 products)      acc_a += W_res[chunk] xn  (bf16x3, 6 products)
+//                          (RF16, round 10: xn as two half planes, acc_a += W_res[chunk] xn on f16x2, 3 products, scaled back once behind the loop)
 //   then:                  q = acc_q + b_q; column max / sum(exp) over the 32 pixel lanes of a wave (pixels are numbered column-major:
 //                          a wave holds (half) a column; DPP + one xor-16 shuffle), the two waves of a 64-row column meet in LDS;
 //                          p -> bf16 planes in the wave's own LDS region -> acc_a += M_b[32-channel block] p  (bf16x3) ; + bias ; store.
@@ -40,6 +41,8 @@ struct LaFuseArgs {
     const float* wq;         // q.1 as f16x2 planes (ddif_net.cpp pack_conv_f16, ck = 32): [n-block][chunk][k16][hi | lo][256 floats]
     int nchq;                // 32-channel chunks of q.1 (= NBQ)
     const float* bq;         // q.1 bias [fea]
+    const float* wres16;     // attn_res as f16x2 planes (pack_conv_f16 of W_res alone, ck = 32), the RF16 kernels only: [n-block][chunk][k16][hi | lo][256 floats]
+    int nchr;                // 32-channel chunks of that pack (= NBQ)
     const float* wmix;       // per-sample bf16x3 planes of [M_b | W_res] (pack_mix_weights_x3_kernel, ck = 32): [n-block][chunk][k16][3][256]
     long long wmix_bstride;  // floats per sample
     int nch_mix;             // 32-channel chunks of that pack (= 2 * NBQ)
@@ -50,20 +53,25 @@ struct LaFuseArgs {
     int xcd;                 // wg_work_range: XCD-contiguous work partition (ddif_dev.h)
 };
 
-template <int TH, int TW, int NBQ, int NBA>
+// RF16: attn_res(xn) on f16x2 -- xn as two half planes, W_res from its own static pack (a.wres16) -- instead of bf16x3 out of the per-sample pack
+// CS = 2 (round 10): the output channels of a 32-pixel block split over two wavefronts -- 64 pixels on four waves (see the kernel)
+template <int TH, int TW, int NBQ, int NBA, bool RF16 = false, int CS = 1>
 struct LaFuseGeom {
-    static constexpr int NPX = TH * TW, NWV = NPX / 32;  // pixels / wavefronts of a workgroup (256 / 8, or 128 / 4: round 6)
+    static constexpr int NPX = TH * TW, NWV = CS * NPX / 32;  // pixels / wavefronts of a workgroup (256 / 8, or 128 / 4: round 6; CS = 2: 64 / 4)
     static constexpr int HH = TH + 2, HW = TW + 2;      // halo tile
     static constexpr int LDH = 24;                      // floats per halo pixel (16 channels + pad: conflict-free depthwise reads)
     static constexpr int LDQ = 20;                      // dwq: 2 half planes x 32 B + 16 B pad
-    static constexpr int LDX = 28;                      // xn: 3 bf16 planes x 32 B + 16 B pad
+    static constexpr int NPR = RF16 ? 2 : 3;            // operand planes of attn_res(xn)
+    static constexpr int LDX = 8 * NPR + 4;             // xn: 3 bf16 planes (or 2 half planes) x 32 B + 16 B pad
     static constexpr int APS = 60;                      // p: 2 slabs x (3 planes x 32 B) + pad, floats per pixel (conflict-free fragment reads)
     static constexpr int HS = HH * HW * LDH, AQ = NPX * LDQ, AX = NPX * LDX;
-    static constexpr int NPC = 2 * NBQ + 3 * NBA;       // 1 KiB weight pieces of one chunk: q.1 (hi | lo per block), attn_res (3 planes per block)
+    static constexpr int NPC = 2 * NBQ + NPR * NBA;     // 1 KiB weight pieces of one chunk: q.1 (hi | lo per block), attn_res (3 planes per block; RF16: hi | lo)
     static constexpr int WC = NPC * 256;                // floats
     static constexpr int NPF = 6 * NBA;                 // pieces of one 32-channel block of M_b: [block][k16][plane]
-    static constexpr int FM = 2 * NPF * 256;            // double-buffered by block parity
-    static constexpr int AP = NPX * APS;                // aliases Hs | Aq | Ax once the chunk loop is over (written behind the first block's barrier)
+    static constexpr int FM = CS == 2 ? 0 : 2 * NPF * 256;  // double-buffered by block parity (CS = 2: the fragments never touch LDS)
+    static constexpr int TWS = NWV * 32 * 36;           // the per-wave fp32 transpose tiles of the softmax section
+    // aliases Hs | Aq | Ax once the chunk loop is over (written behind the first block's barrier); CS = 2: transpose tiles + the p planes of ALL q blocks, shared by the wave pair
+    static constexpr int AP = CS == 2 ? TWS + NBQ * NPX * APS : NPX * APS;
     static constexpr int FEA = 32 * NBQ;
     static constexpr int TAB = 2 * FEA + 9 * FEA + FEA + 32 * NBA;  // gamma | beta | depthwise | q bias | output bias
     static constexpr int CST = 2 * NWV * 32 * 2;        // (max, sum) exchange of the wave pairs of 64-row columns, double-buffered by block parity: [parity][wave][j][max | sum]
@@ -130,11 +138,22 @@ __device__ __forceinline__ float half_allsum(float v) {
 // weights shared through LDS), and the kernel is bound by vector issue with two waves per SIMD: when the eight-wave grid would leave CUs idle (16 x 16 level at
 // B = 64: 64 workgroups; every level at 8-16 tiles per GPU) the host launches twice as many four-wave workgroups and every wave has a SIMD to itself.  Same
 // per-pixel arithmetic in the same order: results do not depend on the choice (tests/test_env_switches.py DDIF_LA_NW).
-template <int TH, int TW, int NBQ, int NBA, int ABL = 0>
-__global__ __launch_bounds__(TH * TW * 2) void linattn_fused_kernel(LaFuseArgs a) {
-    using G = LaFuseGeom<TH, TW, NBQ, NBA>;
+// RF16 (round 10): W_res xn as three f16x2 products per chunk instead of six bf16x3 ones.  xn is GroupNorm's output, which the plan has bounded inside the scaled half range
+// (the rule of attn_block's qkv); the accumulator carries the two operand scales through the chunk loop and is multiplied by the exact power of two that undoes them
+// ONCE, before the bf16x3 M_b p products accumulate on top.
+// CS = 2 (round 10), the 16 x 16 level when even the four-wave grid leaves half of the CUs idle (B = 64: 128 workgroups): a workgroup is 64 pixels (four image columns) on
+// four waves, wave w owns pixel block w & 1 and the q / output n-blocks of channel half w >> 1 -- half the accumulators and half the dependent MFMA and softmax chain per wave,
+// twice the workgroups.  The softmax is per channel, so a wave normalises its own q blocks alone; it writes their p planes into a tile the two waves of a pixel block share,
+// ONE workgroup barrier, then every wave contracts ALL q blocks of p against its own M_b n-blocks (fragments straight from L2 into operand registers, one q block ahead:
+// nothing to share them with).  Every output element sees the same instructions in the same K order as with CS = 1: bit-identical, so the plan may choose by batch size.
+template <int TH, int TW, int NBQ, int NBA, int ABL = 0, bool RF16 = false, int CS = 1>
+__global__ __launch_bounds__(TH * TW * 2 * CS) void linattn_fused_kernel(LaFuseArgs a) {
+    using G = LaFuseGeom<TH, TW, NBQ, NBA, RF16, CS>;
+    static_assert(CS == 1 || (CS == 2 && TH == 16 && TW == 4 && NBQ % 2 == 0 && NBA % 2 == 0 && ABL == 0), "channel split: 64 pixels of a 16-row image on four waves");
+    constexpr int NBQW = NBQ / CS, NBAW = NBA / CS;  // q / output n-blocks of one wave
+    constexpr int NPR = G::NPR;
     constexpr int NW = G::NWV, NTHR = 64 * NW;
-    static_assert((TH * TW == 256 || TH * TW == 128) && (TH == 16 || TH == 32 || TH == 64), "a workgroup owns 256 or 128 pixels = whole columns of the sample");
+    static_assert((TH * TW == 256 || TH * TW == 128 || CS == 2) && (TH == 16 || TH == 32 || TH == 64), "a workgroup owns 256 or 128 pixels = whole columns of the sample");
     static_assert(TH != 64 || NW % 2 == 0, "64-row columns span a wave pair");
     constexpr int HH = G::HH, HW = G::HW, LDH = G::LDH, LDQ = G::LDQ, LDX = G::LDX, APS = G::APS, FEA = G::FEA;
     constexpr int NCH = 2 * NBQ;                              // 16-channel chunks
@@ -165,6 +184,8 @@ __global__ __launch_bounds__(TH * TW * 2) void linattn_fused_kernel(LaFuseArgs a
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 #endif
     const int h = lane >> 5, j = lane & 31;
+    const int pb = CS == 2 ? (wave & 1) : wave;  // this wave's 32-pixel block
+    const int ch = CS == 2 ? (wave >> 1) : 0;    // ... and channel half
     [[maybe_unused]] int dbg_n = 0;
     auto stamp = [&]() {
 #ifndef DDIF_EMU
@@ -209,6 +230,7 @@ __global__ __launch_bounds__(TH * TW * 2) void linattn_fused_kernel(LaFuseArgs a
             const int p = pc < NPC ? pc : NPC - 1;  // (waves past the end re-read the last piece; not written)
             const float* src;
             if (p < 2 * NBQ) src = a.wq + ((size_t)(((p >> 1) * a.nchq + (k >> 1)) * 2 + (k & 1)) * 2 + (p & 1)) * 256;
+            else if constexpr (RF16) src = a.wres16 + ((size_t)((((p - 2 * NBQ) >> 1) * a.nchr + (k >> 1)) * 2 + (k & 1)) * 2 + ((p - 2 * NBQ) & 1)) * 256;
             else src = wmix_b + ((size_t)((((p - 2 * NBQ) / 3) * a.nch_mix + ((NCH + k) >> 1)) * 2 + (k & 1)) * 3 + (p - 2 * NBQ) % 3) * 256;
             wst[i] = (ABL & 2) ? make_float4(1e-3f, 2e-3f, 3e-3f, (float)k) : *reinterpret_cast<const float4*>(src + lane * 4);
         }
@@ -292,18 +314,35 @@ __global__ __launch_bounds__(TH * TW * 2) void linattn_fused_kernel(LaFuseArgs a
             gn_finalize_wave(a.st0, a.np0, a.st1, a.np1, b, (double)FEA * a.H * a.W, &mean, &rstd);
             gn_b = b;
         }
-        f32x16 accq[NBQ], acca[NBA];
+        f32x16 accq[NBQW], acca[NBAW];
 #pragma unroll
-        for (int nb = 0; nb < NBQ; ++nb)
+        for (int nb = 0; nb < NBQW; ++nb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) accq[nb][r] = 0.f;
 #pragma unroll
-        for (int nb = 0; nb < NBA; ++nb)
+        for (int nb = 0; nb < NBAW; ++nb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acca[nb][r] = 0.f;
         const float* wmix_b = a.wmix + (size_t)b * a.wmix_bstride;
-        if constexpr (!(ABL & 16)) load_mix(wmix_b, 0);  // block 0 of M_b: requested before the chunk loop, written to LDS behind it
+        if constexpr (!(ABL & 16) && CS == 1) load_mix(wmix_b, 0);  // block 0 of M_b: requested before the chunk loop, written to LDS behind it
 
+        // xn of pixel p, channel quad c4 of the chunk -> Ax: three bf16 planes, or (RF16) two half planes of xn * 2^4
+        auto store_xn = [&](int p, const float4& v) {
+            if constexpr (RF16) {
+                unsigned h01, l01, h23, l23;
+                dd_split2_pair(v.x * DDIF_F16_ASCALE, v.y * DDIF_F16_ASCALE, &h01, &l01);
+                dd_split2_pair(v.z * DDIF_F16_ASCALE, v.w * DDIF_F16_ASCALE, &h23, &l23);
+                *reinterpret_cast<uint2*>(&Ax[p * LDX + 2 * c4]) = make_uint2(h01, h23);
+                *reinterpret_cast<uint2*>(&Ax[p * LDX + 8 + 2 * c4]) = make_uint2(l01, l23);
+            } else {
+                unsigned h01, m01, l01, h23, m23, l23;
+                dd_split3_pair(v.x, v.y, &h01, &m01, &l01);
+                dd_split3_pair(v.z, v.w, &h23, &m23, &l23);
+                *reinterpret_cast<uint2*>(&Ax[p * LDX + 2 * c4]) = make_uint2(h01, h23);
+                *reinterpret_cast<uint2*>(&Ax[p * LDX + 8 + 2 * c4]) = make_uint2(m01, m23);
+                *reinterpret_cast<uint2*>(&Ax[p * LDX + 16 + 2 * c4]) = make_uint2(l01, l23);
+            }
+        };
 #pragma unroll 1
         for (int k = 0; k < NCH; ++k) {
             stamp();  // 0: chunk start
@@ -378,13 +417,7 @@ __global__ __launch_bounds__(TH * TW * 2) void linattn_fused_kernel(LaFuseArgs a
                         }
                     }
                     if (r == 1 || r == 2) {  // the centre tap of pixel a / b IS xn = GroupNorm(cat[h, skip]): three bf16 planes, written at once (nothing kept)
-                        const int p = p0 + (r - 1);
-                        unsigned h01, m01, l01, h23, m23, l23;
-                        dd_split3_pair(hv[1].x, hv[1].y, &h01, &m01, &l01);
-                        dd_split3_pair(hv[1].z, hv[1].w, &h23, &m23, &l23);
-                        *reinterpret_cast<uint2*>(&Ax[p * LDX + 2 * c4]) = make_uint2(h01, h23);
-                        *reinterpret_cast<uint2*>(&Ax[p * LDX + 8 + 2 * c4]) = make_uint2(m01, m23);
-                        *reinterpret_cast<uint2*>(&Ax[p * LDX + 16 + 2 * c4]) = make_uint2(l01, l23);
+                        store_xn(p0 + (r - 1), hv[1]);
                     }
                     DDIF_SCHED_FENCE();
                 }
@@ -404,7 +437,7 @@ __global__ __launch_bounds__(TH * TW * 2) void linattn_fused_kernel(LaFuseArgs a
             //     pixels are numbered column-major: p = x * TH + y.  One tap ROW at a time (3 + 3 LDS reads in flight): all 18 reads of an
             //     item hoisted, as hipcc prefers, cost 72 registers and pushed the accumulators into scratch.
 #pragma unroll
-            for (int it = 0; it < ((ABL & 8) ? 0 : 2); ++it) {
+            for (int it = 0; it < ((ABL & 8) ? 0 : 4 * TH * TW / NTHR); ++it) {
                 const int item = tid + it * NTHR, p = item >> 2;
                 const int x = p / TH, y = p % TH;
                 float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
@@ -432,12 +465,7 @@ __global__ __launch_bounds__(TH * TW * 2) void linattn_fused_kernel(LaFuseArgs a
                 dd_split2_pair(s2 * DDIF_F16_ASCALE, s3 * DDIF_F16_ASCALE, &h23, &l23);
                 *reinterpret_cast<uint2*>(&Aq[p * LDQ + 2 * c4]) = make_uint2(h01, h23);
                 *reinterpret_cast<uint2*>(&Aq[p * LDQ + 8 + 2 * c4]) = make_uint2(l01, l23);
-                unsigned m01, m23;
-                dd_split3_pair(cen.x, cen.y, &h01, &m01, &l01);
-                dd_split3_pair(cen.z, cen.w, &h23, &m23, &l23);
-                *reinterpret_cast<uint2*>(&Ax[p * LDX + 2 * c4]) = make_uint2(h01, h23);
-                *reinterpret_cast<uint2*>(&Ax[p * LDX + 8 + 2 * c4]) = make_uint2(m01, m23);
-                *reinterpret_cast<uint2*>(&Ax[p * LDX + 16 + 2 * c4]) = make_uint2(l01, l23);
+                store_xn(p, cen);
             }
             }
             store_weights();
@@ -446,46 +474,54 @@ __global__ __launch_bounds__(TH * TW * 2) void linattn_fused_kernel(LaFuseArgs a
             stamp();  // 4: barrier
             // (d) contraction of the chunk: this wave's 32 pixels x all output channels; weight fragments from LDS (1 KiB conflict-free reads)
             {
-                const int p = 32 * wave + j;
-                float4 xq[2], xr[3];
+                const int p = 32 * pb + j;
+                float4 xq[2], xr[NPR];
 #pragma unroll
                 for (int pl = 0; pl < 2; ++pl) xq[pl] = *reinterpret_cast<const float4*>(&Aq[p * LDQ + pl * 8 + 4 * h]);
 #pragma unroll
-                for (int pl = 0; pl < 3; ++pl) xr[pl] = *reinterpret_cast<const float4*>(&Ax[p * LDX + pl * 8 + 4 * h]);
+                for (int pl = 0; pl < NPR; ++pl) xr[pl] = *reinterpret_cast<const float4*>(&Ax[p * LDX + pl * 8 + 4 * h]);
 #pragma unroll
-                for (int nb = 0; nb < NBQ; ++nb) {
+                for (int i = 0; i < NBQW; ++i) {
+                    const int nb = ch * NBQW + i;
                     const float4 f0 = *reinterpret_cast<const float4*>(&Wc[(2 * nb + 0) * 256 + lane * 4]);
                     const float4 f1 = *reinterpret_cast<const float4*>(&Wc[(2 * nb + 1) * 256 + lane * 4]);
-                    f32x16 c = accq[nb];
+                    f32x16 c = accq[i];
                     if (ABL & 4) {
                         c[0] += f1.x * xq[0].x + f0.y * xq[1].y;
-                        accq[nb] = c;
+                        accq[i] = c;
                         continue;
                     }
                     // D = X W: rows = the wave's pixels, columns = the block's q channels (see the softmax section) -- the products and their order are those of W X
                     c = DDIF_MFMA_32x32x16_F16(xq[0], f1, c);  // hi * lo
                     c = DDIF_MFMA_32x32x16_F16(xq[1], f0, c);  // lo * hi
                     c = DDIF_MFMA_32x32x16_F16(xq[0], f0, c);  // hi * hi
-                    accq[nb] = c;
+                    accq[i] = c;
                 }
 #pragma unroll
-                for (int nb = 0; nb < NBA; ++nb) {
-                    float4 f[3];
+                for (int i = 0; i < NBAW; ++i) {
+                    const int nb = ch * NBAW + i;
+                    float4 f[NPR];
 #pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) f[pl] = *reinterpret_cast<const float4*>(&Wc[(2 * NBQ + 3 * nb + pl) * 256 + lane * 4]);
-                    f32x16 c = acca[nb];
+                    for (int pl = 0; pl < NPR; ++pl) f[pl] = *reinterpret_cast<const float4*>(&Wc[(2 * NBQ + NPR * nb + pl) * 256 + lane * 4]);
+                    f32x16 c = acca[i];
                     if (ABL & 4) {
-                        c[0] += f[2].x * xr[0].x + f[1].y * xr[1].y + f[0].z * xr[2].z;
-                        acca[nb] = c;
+                        c[0] += f[NPR - 1].x * xr[0].x + f[1].y * xr[1].y + f[0].z * xr[NPR - 1].z;
+                        acca[i] = c;
                         continue;
                     }
-                    c = DDIF_MFMA_32x32x16_BF16(f[2], xr[0], c);
-                    c = DDIF_MFMA_32x32x16_BF16(f[0], xr[2], c);
-                    c = DDIF_MFMA_32x32x16_BF16(f[1], xr[1], c);
-                    c = DDIF_MFMA_32x32x16_BF16(f[1], xr[0], c);
-                    c = DDIF_MFMA_32x32x16_BF16(f[0], xr[1], c);
-                    c = DDIF_MFMA_32x32x16_BF16(f[0], xr[0], c);
-                    acca[nb] = c;
+                    if constexpr (RF16) {
+                        c = DDIF_MFMA_32x32x16_F16(f[1], xr[0], c);  // lo * hi
+                        c = DDIF_MFMA_32x32x16_F16(f[0], xr[1], c);  // hi * lo
+                        c = DDIF_MFMA_32x32x16_F16(f[0], xr[0], c);  // hi * hi
+                    } else {
+                        c = DDIF_MFMA_32x32x16_BF16(f[2], xr[0], c);
+                        c = DDIF_MFMA_32x32x16_BF16(f[0], xr[2], c);
+                        c = DDIF_MFMA_32x32x16_BF16(f[1], xr[1], c);
+                        c = DDIF_MFMA_32x32x16_BF16(f[1], xr[0], c);
+                        c = DDIF_MFMA_32x32x16_BF16(f[0], xr[1], c);
+                        c = DDIF_MFMA_32x32x16_BF16(f[0], xr[0], c);
+                    }
+                    acca[i] = c;
                 }
             }
             stamp();  // 5: contraction issued
@@ -501,10 +537,102 @@ __global__ __launch_bounds__(TH * TW * 2) void linattn_fused_kernel(LaFuseArgs a
         //      p = e^(q - m_w) e^(m_w - M) / (S_w e^(m_w - M) + S_p e^(m_p - M)) -- behind the barrier that publishes the block's M_b fragments.
         //      p goes back to the pixel-per-lane operand layout through a per-wave fp32 tile in LDS ([32 pixels][32 channels + 4]), is split into bf16 planes on the
         //      way out and feeds a += M_b p straight from registers.
+        if constexpr (RF16) {  // W_res xn is complete: back from the operand scales (2^-14, exact) before M_b p accumulates on top
+#pragma unroll
+            for (int nb = 0; nb < NBAW; ++nb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acca[nb][r] *= DDIF_F16_OSCALE;
+        }
         constexpr int NCW = (TH == 16) ? 2 : 1;  // image columns per wavefront
         constexpr int RPC = 16 / NCW;            // accumulator registers per column
         constexpr int TLD = 36;                  // floats per pixel row of the transpose tile (9 sixteen-byte slots: conflict-free float4 reads)
         float* Tw = Ap + wave * (32 * TLD);
+        if constexpr (CS == 2) {
+            static_assert(G::TWS == G::NWV * 32 * TLD, "transpose tiles");
+            float* Pp = Ap + G::TWS;  // [pixel block][q block][32 pixels][APS]: the p planes, B-fragment order per pixel (2 slabs x 3 planes x 32 B)
+            // the M_b fragments of this wave's output blocks, q block nb: 6 NBAW pieces of 1 KiB
+            float4 fm[2][NBAW][2][3];
+            auto load_frag = [&](int nb, float4 (*f)[2][3]) {
+#pragma unroll
+                for (int na = 0; na < NBAW; ++na)
+#pragma unroll
+                    for (int k16 = 0; k16 < 2; ++k16)
+#pragma unroll
+                        for (int pl = 0; pl < 3; ++pl)
+                            f[na][k16][pl] = *reinterpret_cast<const float4*>(wmix_b + ((size_t)((((ch * NBAW + na) * a.nch_mix + nb) * 2 + k16) * 3 + pl)) * 256 + lane * 4);
+            };
+            load_frag(0, fm[0]);
+            __syncthreads();  // every wave is past the last chunk's fragment reads (Ap aliases Hs, Aq, Ax)
+#pragma unroll
+            for (int i = 0; i < NBQW; ++i) {
+                DDIF_SCHED_FENCE();
+                const int nb = ch * NBQW + i;
+                float e[16], sm[NCW];
+                const float bj = BQ[32 * nb + j];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) e[r] = fmaf(accq[i][r], DDIF_F16_OSCALE, bj);
+#pragma unroll
+                for (int cg = 0; cg < NCW; ++cg) {
+                    float m = e[cg * RPC];
+#pragma unroll
+                    for (int r = 1; r < RPC; ++r) m = fmaxf(m, e[cg * RPC + r]);
+                    m = fmaxf(m, __shfl_xor(m, 32));
+                    float sacc = 0.f;
+#pragma unroll
+                    for (int r = 0; r < RPC; ++r) {
+                        const float ex = dd_exp2_fast((e[cg * RPC + r] - m) * L2E);
+                        e[cg * RPC + r] = ex;
+                        sacc += ex;
+                    }
+                    sacc += __shfl_xor(sacc, 32);
+                    sm[cg] = sacc;
+                }
+                float fac[NCW];
+#pragma unroll
+                for (int cg = 0; cg < NCW; ++cg) fac[cg] = dd_rcp_fast(sm[cg]);
+                if (i > 0) DDIF_WAVE_LDS_SYNC();  // the previous block's tile reads are done
+#pragma unroll
+                for (int r = 0; r < 16; ++r) Tw[((r >> 2) * 8 + 4 * h + (r & 3)) * TLD + j] = e[r] * fac[r / RPC];
+                DDIF_WAVE_LDS_SYNC();
+#pragma unroll
+                for (int k16 = 0; k16 < 2; ++k16) {
+                    const float4 t0 = *reinterpret_cast<const float4*>(&Tw[j * TLD + 16 * k16 + 8 * h]);
+                    const float4 t1 = *reinterpret_cast<const float4*>(&Tw[j * TLD + 16 * k16 + 8 * h + 4]);
+                    unsigned hh[4], mm[4], ll[4];
+                    dd_split3_pair(t0.x, t0.y, &hh[0], &mm[0], &ll[0]);
+                    dd_split3_pair(t0.z, t0.w, &hh[1], &mm[1], &ll[1]);
+                    dd_split3_pair(t1.x, t1.y, &hh[2], &mm[2], &ll[2]);
+                    dd_split3_pair(t1.z, t1.w, &hh[3], &mm[3], &ll[3]);
+                    unsigned* d = reinterpret_cast<unsigned*>(&Pp[((pb * NBQ + nb) * 32 + j) * APS + k16 * 24 + 4 * h]);
+                    *reinterpret_cast<uint4*>(d) = make_uint4(hh[0], hh[1], hh[2], hh[3]);
+                    *reinterpret_cast<uint4*>(d + 8) = make_uint4(mm[0], mm[1], mm[2], mm[3]);
+                    *reinterpret_cast<uint4*>(d + 16) = make_uint4(ll[0], ll[1], ll[2], ll[3]);
+                }
+            }
+            __syncthreads();  // p complete: both channel halves of every pixel block
+#pragma unroll
+            for (int nb = 0; nb < NBQ; ++nb) {
+                if (nb + 1 < NBQ) load_frag(nb + 1, fm[(nb + 1) & 1]);
+#pragma unroll
+                for (int k16 = 0; k16 < 2; ++k16) {
+                    float4 xp[3];
+#pragma unroll
+                    for (int pl = 0; pl < 3; ++pl) xp[pl] = *reinterpret_cast<const float4*>(&Pp[((pb * NBQ + nb) * 32 + j) * APS + k16 * 24 + pl * 8 + 4 * h]);
+#pragma unroll
+                    for (int na = 0; na < NBAW; ++na) {
+                        const float4* f = fm[nb & 1][na][k16];
+                        f32x16 c = acca[na];
+                        c = DDIF_MFMA_32x32x16_BF16(f[2], xp[0], c);
+                        c = DDIF_MFMA_32x32x16_BF16(f[0], xp[2], c);
+                        c = DDIF_MFMA_32x32x16_BF16(f[1], xp[1], c);
+                        c = DDIF_MFMA_32x32x16_BF16(f[1], xp[0], c);
+                        c = DDIF_MFMA_32x32x16_BF16(f[0], xp[1], c);
+                        c = DDIF_MFMA_32x32x16_BF16(f[0], xp[0], c);
+                        acca[na] = c;
+                    }
+                }
+            }
+        } else {
 #pragma unroll
         for (int nb = 0; nb < ((ABL & 16) ? 0 : NBQ); ++nb) {
             DDIF_SCHED_FENCE();
@@ -590,18 +718,19 @@ __global__ __launch_bounds__(TH * TW * 2) void linattn_fused_kernel(LaFuseArgs a
                 }
             }
         }
+        }
         DDIF_SCHED_FENCE();
         stamp();  // softmax + attn_out done
         // ---- epilogue: + bias, NHWC float4 stores
         {
-            const int p = 32 * wave + j, x = x0 + p / TH, y = p % TH;
+            const int p = 32 * pb + j, x = x0 + p / TH, y = p % TH;
             if (x < a.W) {
                 float* o = a.out + ((size_t)(b * a.H + y) * a.W + x) * a.dout;
 #pragma unroll
-                for (int na = 0; na < NBA; ++na)
+                for (int na = 0; na < NBAW; ++na)
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        const int co = 32 * na + 8 * g + 4 * h;
+                        const int co = 32 * (ch * NBAW + na) + 8 * g + 4 * h;
                         if (co < a.dout) {
                             const float4 bo = *reinterpret_cast<const float4*>(&BO[co]);
                             if (!(ABL & 32) || acca[na][4 * g] == 12345.678f)

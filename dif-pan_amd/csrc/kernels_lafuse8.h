@@ -14,7 +14,8 @@
 //     chunk loop (64 input channels at a time):  raw halo tile (registers, prefetched one chunk ahead) -> GroupNorm -> Hs (fp32, LDS) | barrier |
 //         depthwise 3x3 -> dwq as two half planes, centre of Hs -> xn as three bf16 planes | barrier |
 //         wave w:  acc_q[32 pixels x q channels 32 w ..]  += W_q[w][chunk] dwq      (3 products x 4 slabs)
-//                  acc_a[32 pixels x out channels 32 (w & 3) ..] += W_res[w & 3][slabs 2 (w >> 2), + 1 of the chunk] xn   (6 products x 2 slabs)
+//                  acc_a[32 pixels x out channels 32 (w & 3) ..] += W_res[w & 3][slabs 2 (w >> 2), + 1 of the chunk] xn   (6 products x 2 slabs;
+//                  RF16, round 10: xn as two half planes and W_res from its own f16x2 pack, 3 products x 2 slabs, scaled back once behind the loop)
 //     the B fragments (weights) are not shared between waves and never touch LDS: each wave reads its own pre-packed 1 KiB pieces straight from L2 into the
 //     MFMA operand registers, requested at the top of the chunk and consumed behind its two staging stages;
 //     softmax over the 8 rows of a column = over 8 neighbouring lanes (pixels are numbered column-major): three DPP steps per value; p -> LDS as bf16 planes;
@@ -24,13 +25,14 @@
 
 namespace ddif {
 
-template <int NBQ>
+template <int NBQ, bool RF16 = false>  // RF16: attn_res(xn) on f16x2 (kernels_lafuse.h)
 struct LaFuse8Geom {
     static constexpr int FEA = 32 * NBQ, NCHK = FEA / 64, NS = FEA / 16;  // channels, 64-channel chunks, 16-channel slabs
     static constexpr int HW = 6, HH = 10, NHP = HW * HH;                  // halo tile: 6 columns x 10 rows
     static constexpr int LDH = 68;                                        // floats per halo pixel: 64 channels + 16 B pad
     static constexpr int LDQ = 68;                                        // dwq: 4 slabs x 2 half planes x 32 B + 16 B pad
-    static constexpr int LDX = 100;                                       // xn:  4 slabs x 3 bf16 planes x 32 B + 16 B pad
+    static constexpr int NPR = RF16 ? 2 : 3;                              // operand planes of attn_res(xn)
+    static constexpr int LDX = 4 * 8 * NPR + 4;                           // xn:  4 slabs x 3 bf16 planes (or 2 half planes) x 32 B + 16 B pad
     static constexpr int LDP = NS * 24 + 4;                               // p:   NS slabs x 3 bf16 planes x 32 B + 16 B pad (odd in 16-byte slots: conflict-free fragment reads)
     static constexpr int HS = NHP * LDH, AQ = 32 * LDQ, AX = 32 * LDX, AP = 32 * LDP;
     static constexpr int MAIN = (HS + AQ + AX) > AP ? (HS + AQ + AX) : AP;  // Ap aliases Hs | Aq | Ax once the chunk loop is over
@@ -67,9 +69,10 @@ __device__ __forceinline__ float oct_allsum(float v) {
 
 // LaFuseArgs as for linattn_fused_kernel with H = W = 8, c0 % 64 == 0, c1 % 64 == 0, c0 + c1 = 32 NBQ, dout = 128.
 // ABL (tools/mbench_la8.cpp only): 64 = s_memtime stamps of thread 0 into a.dbg, 128 = six more per 64-channel chunk
-template <int NBQ, int ABL = 0>
+template <int NBQ, int ABL = 0, bool RF16 = false>
 __global__ __launch_bounds__(512) void linattn8_fused_kernel(LaFuseArgs a) {
-    using G = LaFuse8Geom<NBQ>;
+    using G = LaFuse8Geom<NBQ, RF16>;
+    constexpr int NPR = G::NPR;
     constexpr int FEA = G::FEA, NCHK = G::NCHK, NS = G::NS, HW = G::HW, HH = G::HH, NHP = G::NHP;
     constexpr int LDH = G::LDH, LDQ = G::LDQ, LDX = G::LDX, LDP = G::LDP;
     constexpr int NSH = NS / 2;       // slabs of one K half of the M_b contraction
@@ -189,7 +192,7 @@ __global__ __launch_bounds__(512) void linattn8_fused_kernel(LaFuseArgs a) {
         }
         const float* wmix_b = a.wmix + (size_t)b * a.wmix_bstride;
         const float* wq_w = a.wq + (size_t)(qw ? wave : 0) * a.nchq * (2 * 2 * 256);  // (waves without a q block re-read block 0; never consumed)
-        const float* wr_w = wmix_b + ((size_t)nr * a.nch_mix + NBQ + kh) * (2 * 3 * 256);
+        const float* wr_w = RF16 ? a.wres16 + ((size_t)nr * a.nchr + kh) * (2 * 2 * 256) : wmix_b + ((size_t)nr * a.nch_mix + NBQ + kh) * (2 * 3 * 256);
         // this wave's weight pieces (1 KiB each, lane-linear): wave-uniform base + 32-bit lane offset
         unsigned lo4 = (unsigned)lane * 4u;
 #ifndef DDIF_EMU
@@ -201,9 +204,9 @@ __global__ __launch_bounds__(512) void linattn8_fused_kernel(LaFuseArgs a) {
             // (a) this chunk's B fragments: requested now, consumed in stage (d)
             // (one wave-uniform base per chunk and constant piece offsets: the per-piece index expressions of the first form cost ~1 k ticks of address
             //  arithmetic per chunk before the fourteen loads were out, tools/mbench_la8.cpp)
-            float4 wqr[4][2], wrr[2][3];
+            float4 wqr[4][2], wrr[2][NPR];
             const float* wqk = wq_w + (size_t)k * (2 * 2 * 2 * 256);   // this wave's q block: two 32-channel chunks x two k16 x two planes per 64-channel chunk
-            const float* wrk = wr_w + (size_t)k * (2 * 2 * 3 * 256);   // this wave's output block / K half: chunk NBQ + 2 k + kh
+            const float* wrk = wr_w + (size_t)k * (2 * 2 * NPR * 256);  // this wave's output block / K half: chunk NBQ + 2 k + kh (RF16: chunk 2 k + kh of W_res' own pack)
 #pragma unroll
             for (int sl = 0; sl < 4; ++sl)
 #pragma unroll
@@ -211,7 +214,7 @@ __global__ __launch_bounds__(512) void linattn8_fused_kernel(LaFuseArgs a) {
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
-                for (int pl = 0; pl < 3; ++pl) wrr[t][pl] = *reinterpret_cast<const float4*>(wrk + (t * 3 + pl) * 256 + lo4);
+                for (int pl = 0; pl < NPR; ++pl) wrr[t][pl] = *reinterpret_cast<const float4*>(wrk + (t * NPR + pl) * 256 + lo4);
             if (ABL & 128) stamp();  // c0: chunk's fragment loads issued
             // (b) GroupNorm of the raw halo tile -> Hs (zero padding comes after the normalisation: the depthwise conv pads xn)
             {
@@ -268,16 +271,23 @@ __global__ __launch_bounds__(512) void linattn8_fused_kernel(LaFuseArgs a) {
                     if (ty == 1) cen = hv[1];
                 }
                 const int sl = c4 >> 2, e2 = (c4 & 3) * 2;  // slab of the chunk, float offset of this quad's 4 halves inside a plane
-                unsigned h01, l01, h23, l23, m01, m23;
+                [[maybe_unused]] unsigned h01, l01, h23, l23, m01, m23;
                 dd_split2_pair(s0 * DDIF_F16_ASCALE, s1 * DDIF_F16_ASCALE, &h01, &l01);
                 dd_split2_pair(s2 * DDIF_F16_ASCALE, s3 * DDIF_F16_ASCALE, &h23, &l23);
                 *reinterpret_cast<uint2*>(&Aq[p * LDQ + sl * 16 + e2]) = make_uint2(h01, h23);
                 *reinterpret_cast<uint2*>(&Aq[p * LDQ + sl * 16 + 8 + e2]) = make_uint2(l01, l23);
-                dd_split3_pair(cen.x, cen.y, &h01, &m01, &l01);
-                dd_split3_pair(cen.z, cen.w, &h23, &m23, &l23);
-                *reinterpret_cast<uint2*>(&Ax[p * LDX + sl * 24 + e2]) = make_uint2(h01, h23);
-                *reinterpret_cast<uint2*>(&Ax[p * LDX + sl * 24 + 8 + e2]) = make_uint2(m01, m23);
-                *reinterpret_cast<uint2*>(&Ax[p * LDX + sl * 24 + 16 + e2]) = make_uint2(l01, l23);
+                if constexpr (RF16) {
+                    dd_split2_pair(cen.x * DDIF_F16_ASCALE, cen.y * DDIF_F16_ASCALE, &h01, &l01);
+                    dd_split2_pair(cen.z * DDIF_F16_ASCALE, cen.w * DDIF_F16_ASCALE, &h23, &l23);
+                    *reinterpret_cast<uint2*>(&Ax[p * LDX + sl * 16 + e2]) = make_uint2(h01, h23);
+                    *reinterpret_cast<uint2*>(&Ax[p * LDX + sl * 16 + 8 + e2]) = make_uint2(l01, l23);
+                } else {
+                    dd_split3_pair(cen.x, cen.y, &h01, &m01, &l01);
+                    dd_split3_pair(cen.z, cen.w, &h23, &m23, &l23);
+                    *reinterpret_cast<uint2*>(&Ax[p * LDX + sl * 24 + e2]) = make_uint2(h01, h23);
+                    *reinterpret_cast<uint2*>(&Ax[p * LDX + sl * 24 + 8 + e2]) = make_uint2(m01, m23);
+                    *reinterpret_cast<uint2*>(&Ax[p * LDX + sl * 24 + 16 + e2]) = make_uint2(l01, l23);
+                }
             }
             if (ABL & 128) stamp();  // c3: depthwise + split stage done
             __syncthreads();
@@ -296,20 +306,30 @@ __global__ __launch_bounds__(512) void linattn8_fused_kernel(LaFuseArgs a) {
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int sl = 2 * kh + t;
-                float4 xr[3];
+                float4 xr[NPR];
 #pragma unroll
-                for (int pl = 0; pl < 3; ++pl) xr[pl] = *reinterpret_cast<const float4*>(&Ax[j * LDX + sl * 24 + pl * 8 + 4 * h]);
-                acca = DDIF_MFMA_32x32x16_BF16(wrr[t][2], xr[0], acca);
-                acca = DDIF_MFMA_32x32x16_BF16(wrr[t][0], xr[2], acca);
-                acca = DDIF_MFMA_32x32x16_BF16(wrr[t][1], xr[1], acca);
-                acca = DDIF_MFMA_32x32x16_BF16(wrr[t][1], xr[0], acca);
-                acca = DDIF_MFMA_32x32x16_BF16(wrr[t][0], xr[1], acca);
-                acca = DDIF_MFMA_32x32x16_BF16(wrr[t][0], xr[0], acca);
+                for (int pl = 0; pl < NPR; ++pl) xr[pl] = *reinterpret_cast<const float4*>(&Ax[j * LDX + sl * 8 * NPR + pl * 8 + 4 * h]);
+                if constexpr (RF16) {
+                    acca = DDIF_MFMA_32x32x16_F16(wrr[t][1], xr[0], acca);  // lo * hi
+                    acca = DDIF_MFMA_32x32x16_F16(wrr[t][0], xr[1], acca);  // hi * lo
+                    acca = DDIF_MFMA_32x32x16_F16(wrr[t][0], xr[0], acca);  // hi * hi
+                } else {
+                    acca = DDIF_MFMA_32x32x16_BF16(wrr[t][2], xr[0], acca);
+                    acca = DDIF_MFMA_32x32x16_BF16(wrr[t][0], xr[2], acca);
+                    acca = DDIF_MFMA_32x32x16_BF16(wrr[t][1], xr[1], acca);
+                    acca = DDIF_MFMA_32x32x16_BF16(wrr[t][1], xr[0], acca);
+                    acca = DDIF_MFMA_32x32x16_BF16(wrr[t][0], xr[1], acca);
+                    acca = DDIF_MFMA_32x32x16_BF16(wrr[t][0], xr[0], acca);
+                }
             }
             if (ABL & 128) stamp();  // c5: contraction issued (includes the wait for the fragments)
             // (no barrier here: the next chunk's GroupNorm stage writes Hs, which nobody reads any more; Aq / Ax are rewritten behind its barrier)
         }
         stamp();
+        if constexpr (RF16) {  // this wave's K half of W_res xn is complete: back from the operand scales (2^-14, exact) before M_b p accumulates on top
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acca[r] *= DDIF_F16_OSCALE;
+        }
 
         // ---- M_b fragments of this wave's K half, first round: in flight during the softmax
         float4 wm0[NR0][3], wm1[NR1][3];
