@@ -59,9 +59,8 @@ ConvVariant variant_for_cfg(int cfg) {
     }
     if constexpr (KS == 3 && S == 1 && VEC == 1 && (PRO == PRO_NONE || PRO == PRO_GN_SILU)) {
         switch (cfg) {
-            // f16x2 (MATH = 3): the bf16x3 tilings 7 / 8 / 9 (+ 20).  (A 16x16 x 64-cout tiling on eight waves measured 0.5 % faster on the
-            // step at B = 64 -- 4.75 vs 4.775 ms -- but a cout tile that depends on the item count regroups the GroupNorm partials, and
-            // tiles of a batch are then no longer bit-equal to single-tile runs: not kept.)
+            // f16x2 (MATH = 3): the bf16x3 tilings 7 / 8 / 9 (+ 20).  (The 16x16 x 64-cout tiling on eight waves that rounds 4-5 measured and dropped -- a cout tile
+            // that depends on the item count regrouped the GroupNorm partials -- is cfg 67 below, with the partials of the 32-cout tiling.)
             case 27: v.fn = conv_mfma_kernel<KS, S, U, 16, 16, CK, 8, 1, 1, 1, PRO, VEC, EPI, 0, 3>; v.smem = conv_smem_bytes<KS, S, U, 16, 16, CK, 1, PRO, 8, 3>(); v.th = 16; v.tw = 16; v.nt = 32; v.nthr = 512; v.x3 = v.f16 = true; break;
             case 28: v.fn = conv_mfma_kernel<KS, S, U, 8, 16, CK, 4, 1, 1, 1, PRO, VEC, EPI, 0, 3>; v.smem = conv_smem_bytes<KS, S, U, 8, 16, CK, 1, PRO, 4, 3>(); v.th = 8; v.tw = 16; v.nt = 32; v.x3 = v.f16 = true; break;
             case 29: v.fn = conv_mfma_kernel<KS, S, U, 8, 8, CK, 2, 2, 1, 1, PRO, VEC, EPI, 0, 3>; v.smem = conv_smem_bytes<KS, S, U, 8, 8, CK, 2, PRO, 4, 3>(); v.th = 8; v.tw = 8; v.nt = 64; v.x3 = v.f16 = true; break;
@@ -72,6 +71,18 @@ ConvVariant variant_for_cfg(int cfg) {
             // LDS once per workgroup.  Same pack, same accumulation order, same partials as 27 -- bit-identical results, 3-6 % faster in isolation
             // (profiles/r05/a_mbench_resident.txt).  Chosen by add_conv for 32 -> <= 32 channel convs.
             if (cfg == 37) { v.fn = conv_mfma_kernel<KS, S, U, 16, 16, 32, 8, 1, 1, 1, PRO, VEC, EPI, 0, 5>; v.smem = conv_smem_bytes<KS, S, U, 16, 16, 32, 1, PRO, 8, 5>(); v.th = 16; v.tw = 16; v.nt = 32; v.nthr = 512; v.x3 = v.f16 = v.wr = true; }
+            // 67 / 68 = tilings 27 / 28 with 64-cout work items (NB = 2, round 7): the halo tile is staged, normalised and split once per 64 couts and an item walks
+            // half the stages per cout.  Same pack, same products and K order per (pixel, cout); the statistics partials stay per 32-cout block, at the indices and
+            // in the summation order of 27 / 28 (kernels_conv.h SPLIT) -- bit-identical outputs AND partials, so add_conv may choose by the item count.
+            // Only the epilogues the 64-channel sites of the 64 x 64 / 32 x 32 levels use.  The eight-wave form with a GroupNorm prologue AND residual or per-sample
+            // time-bias operands needs more than the 256 registers two waves per SIMD leave (24 / 36 bytes of scratch per lane, profiles/r11): the GroupNorm sites
+            // (ResnetBlock convs; block1 needs its time-bias twin on the same tiling) have the four-wave form 68 only (one wave per SIMD, 512 registers, no scratch).
+            constexpr bool EIGHT_OK = PRO == PRO_NONE;
+            if constexpr (EPI == 0 || EPI == EPI_RES || EPI == EPI_SILU || EPI == EPI_TBS) {
+                if constexpr (EIGHT_OK)
+                if (cfg == 67) { v.fn = conv_mfma_kernel<KS, S, U, 16, 16, CK, 8, 1, 1, 2, PRO, VEC, EPI, 0, 3>; v.smem = conv_smem_bytes<KS, S, U, 16, 16, CK, 2, PRO, 8, 3, 2>(); v.th = 16; v.tw = 16; v.nt = 64; v.nthr = 512; v.x3 = v.f16 = true; v.nbs = 2; }
+                if (cfg == 68) { v.fn = conv_mfma_kernel<KS, S, U, 8, 16, CK, 4, 1, 1, 2, PRO, VEC, EPI, 0, 3>; v.smem = conv_smem_bytes<KS, S, U, 8, 16, CK, 2, PRO, 4, 3, 2>(); v.th = 8; v.tw = 16; v.nt = 64; v.x3 = v.f16 = true; v.nbs = 2; }
+            }
         }
     }
     if constexpr (KS == 3 && S == 1 && U == 0 && VEC == 2 && PRO == PRO_NONE && EPI == 0) {

@@ -49,8 +49,22 @@ static int xcd_mask() { static const int v = env_int("DDIF_XCD", 15); return v; 
 static int la8_enabled() { static const int v = env_int("DDIF_LA8", 1); return v; }
 // DDIF_XF=0: CondInjection.x_conv + FiLM as a launch of its own everywhere (the form of rounds 1-5); tests/test_env_switches.py
 static int xf_enabled() { static const int v = env_int("DDIF_XF", 1); return v; }
+// DDIF_NB2=0: the f16x2 3x3 convs with >= 64 couts as 32-cout work items everywhere (the launch program of round 6) instead of 64-cout items (conv_variants.h
+// cfg 67 / 68, round 7) where a launch has at least one such item per CU (the default, -1); DDIF_NB2=1: 64-cout items wherever an instantiation exists, whatever
+// the item count (like DDIF_TILE16).  Bit-identical results, partials included: tests/test_conv_nb2.py
+static int nb2_mode() { static const int v = env_int("DDIF_NB2", -1); return v; }
 // DDIF_LR=0: the 8x8 / 16x16 levels on the general conv kernel (kernels_conv.h) as well; covered by tests/test_env_switches.py
 static int lr_enabled() { static const int v = env_int("DDIF_LR", 1); return v; }
+// Can a 64-cout ResnetBlock.block2 at an H x W level carry the next block's 64 -> 64 x_conv + FiLM (add_conv: only as a 64-cout work item, tiling 68)?  The plan
+// builder asks before it makes the request: where the answer is no, nothing about the plan changes -- not even the order of its cond-only program.
+static bool fold64_possible(int B, int H, int W, bool train, int math_mode) {
+    // Only under DDIF_NB2=1, never by the default rule: the fold's y is no bit-for-bit twin of the 1x1 launch, so a site must fold at every batch size or at none (a
+    // tile of a batch stays bit-equal to the tile run alone, tests/test_gpu_batch64.py) -- the item-count rule cannot select it, and folding at every batch size
+    // would change the 132-launch program of small batches, which tests pin.  Measured at B = 64: -12.8 us per site (profiles/r11).
+    if (nb2_mode() <= 0 || !xf_enabled() || train || math_mode != 0 || !x3_enabled() || !f16_enabled()) return false;
+    (void)B;
+    return W >= 16 && !(lr_enabled() && H * W <= 256);
+}
 // 16 x 16-pixel tiles on eight waves where they fill the CUs; below that (8-16 tiles per GPU: what one rank of a strong-scaling run holds) the four-wave
 // 8 x 16 tiling gives twice the workgroups and every wave a SIMD to itself.  Results do not depend on the choice bit for bit: same products per pixel, and
 // the 16 x 16 tilings write their statistics partials per 8 x 16 half tile (ConvArgs::st_halves).  DDIF_TILE16=1 / 0 forces one form.
@@ -359,6 +373,32 @@ int Plan::add_conv(std::vector<Op>& prog, const ConvSpec& s, Tensor* out) {
     if (cfg == 27 && wres_env && c0 == 32 && c1 == 0 && pc.cout <= 32 && pc.ck == 16 && pc.n_chunks == 2 && !s.w_override && s.w_bstride == 0 && variant(37, epi).fn)
         cfg = 37;
     ConvVariant var = variant(cfg, epi);
+    // round 7: 64-cout work items (NB = 2) on the f16x2 tilings 27 / 28 -- the halo tile of a pixel tile is staged, normalised and split once per 64 couts, and the
+    // launch walks half the stages.  The statistics partials stay per 32-cout block (ConvVariant::nbs), so outputs and partials are the bits of the 32-cout items and
+    // the rule may look at the item count: only where every CU still gets an item (small batches keep the finer items).
+    // Tiling 67 (eight waves) where the combination has it, else 68 (conv_variants.h: two eight-wave forms would spill); 27 -> 68 changes the pixel tile as well,
+    // which the half-tile partials of round 6 already make bit-neutral.
+    // Measured at B = 64 (profiles/r11): the sites without a prologue (ffn.0, ffn.3(ffn.2)) gain 1.8 - 2.8 us per launch on 67; the ResnetBlock convs of the 32 x 32
+    // level LOSE 3.4 - 5 us on 68 (one four-wave workgroup per CU against one eight-wave one) and keep their 32-cout items -- except block2 where it can then carry the
+    // next block's x_conv + FiLM (the 64 -> 64 fold below exists on 64-cout items only): 68 + fold replaces two launches, -12 us per site.  The fold changes the bits
+    // of y, so it may not hang on the item count: it is taken under DDIF_NB2=1 only (fold64_possible above).
+    const bool fold64 = nb2_mode() > 0 && s.xf && !train_mode && xf_enabled() && &prog == &step && pc.ks == 3 && pc.cout == 64 && s.tb_off < 0 && !s.samp && s.xf->pc && s.xf->w && s.xf->film &&
+                        s.xf->pc->bias && s.xf->pc->cin == 64 && s.xf->pc->cout == 64 && get_xf_variant(s.stride, s.pro, 68, vec, epi, 2).fn;
+    if ((cfg == 27 || cfg == 28) && var.fn && nb2_mode() != 0 && pc.cout % 64 == 0) {
+        for (int c2 = cfg + 40; c2 <= 68; ++c2) {
+            const int th = c2 == 67 ? 16 : 8;
+            const long items64 = (long)B * ((Hout + th - 1) / th) * ((Wout + 15) / 16) * (pc.cout / 64);
+            const ConvVariant v2 = variant(c2, epi);
+            // (... and never on a launch of fewer than 64 items, whatever the device: the gain is measured on launches of 256 - 1024 items, and a device of a
+            //  few CUs -- the host-emulated one reports 4 -- keeps the launch programs that tests/golden/plan_signature_emu.json pins)
+            const bool pays = s.pro == PRO_NONE && items64 >= num_cus() && items64 >= 64;
+            if ((nb2_mode() > 0 || pays) && v2.fn && (s.tb_off < 0 || variant(c2, epi | EPI_TBS).fn)) {
+                cfg = c2;
+                var = v2;
+                break;
+            }
+        }
+    }
     // the fallback ladder: low-resolution kernel -> general kernel (a prologue / epilogue combination the low-resolution kernel does not carry), and
     // bf16x1 -> the default math of this conv (a combination the throughput variant does not instantiate)
     auto general_kernel_if_no_lr = [&](bool f16, bool b1) {
@@ -387,10 +427,13 @@ int Plan::add_conv(std::vector<Op>& prog, const ConvSpec& s, Tensor* out) {
     // round 6: the next block's x_conv + FiLM as a second output of this conv (kernels_conv.h EPI_XF) -- where the chosen f16x2 tiling has such an instantiation
     // and one wave holds all 32 couts of its pixels; otherwise the request is left undone and the caller emits the 1x1 launch as before
     bool xf = false;
-    if (s.xf && !train_mode && xf_enabled() && var.f16 && !var.lr && pc.ks == 3 && pc.cout == 32 && !s.ups && s.tb_off < 0 && !s.samp && s.xf->pc && s.xf->w && s.xf->film &&
-        s.xf->pc->cin == 32 && s.xf->pc->bias && (s.xf->pc->cout == 32 || s.xf->pc->cout == 64) && &prog == &step) {
+    // round 7: ... or both 32-cout blocks of its pixels, as a 64-cout item (cfg 68): the 64 -> 64 x_conv of the second level's blocks
+    const bool xf32 = pc.cout == 32 && s.xf && s.xf->pc && s.xf->pc->cin == 32 && (s.xf->pc->cout == 32 || s.xf->pc->cout == 64);
+    const bool xf64 = pc.cout == 64 && cfg == 68 && s.xf && s.xf->pc && s.xf->pc->cin == 64 && s.xf->pc->cout == 64;
+    if (s.xf && !train_mode && xf_enabled() && var.f16 && !var.lr && pc.ks == 3 && (xf32 || xf64) && !s.ups && s.tb_off < 0 && !s.samp && s.xf->w && s.xf->film &&
+        s.xf->pc->bias && &prog == &step) {
         const ConvVariant vx = get_xf_variant(s.stride, s.pro, cfg, vec, epi, s.xf->pc->cout / 32);
-        if (vx.fn && vx.smem == var.smem) {
+        if (vx.fn && vx.smem == var.smem + (xf64 ? XF64_LDS_BYTES : 0)) {
             var = vx;
             xf = true;
         }
@@ -456,7 +499,7 @@ int Plan::add_conv(std::vector<Op>& prog, const ConvSpec& s, Tensor* out) {
     a.tiles_y8 = (Hout + 7) / 8;
     const int np_out = st_halves ? a.tiles_x * a.tiles_y8 : a.tiles_x * a.tiles_y;
     if (s.stats) {
-        out->np = np_out * gy;
+        out->np = np_out * gy * var.nbs;  // (64-cout items of cfg 67 / 68: one partial per 32-cout block, the array of cfg 27 / 28)
         if (int e = dalloc(&out->st, (size_t)B * out->np * 2)) return e;
         a.st_out = out->st;
     }
@@ -537,7 +580,7 @@ int Plan::add_conv(std::vector<Op>& prog, const ConvSpec& s, Tensor* out) {
     op.bytes = 4.0 * B * ((double)Hin * Win * (c0 + c1) + (double)Hout * Wout * pc.cout);
     if (xf) {  // + the folded 1x1 conv and its FiLM operands / output
         op.label += " + x_conv+FiLM";
-        op.flop += 2.0 * B * Hout * Wout * 32.0 * s.xf->pc->cout;
+        op.flop += 2.0 * B * Hout * Wout * (double)s.xf->pc->cin * s.xf->pc->cout;
         op.bytes += 4.0 * B * (double)Hout * Wout * 3.0 * s.xf->pc->cout;
     }
     op.cls = (Hout * Wout <= 256) ? 2 : (pc.ks == 3 ? 0 : 1);
@@ -899,6 +942,7 @@ struct PlanBuilder {
         const PackedConv* px = PC(ci + ".x_conv");
         const float* wxf = V(ci + ".x_conv.xf");
         if (!px || !wxf) return 0;
+        if (px->cin == 64 && !fold64_possible(B, cur.H >> (next_lev - lev), cur.W >> (next_lev - lev), train, p.math_mode)) return 0;
         Tensor hid, film;
         DDIF_TRY(film_of(Ln, next_lev, &hid, &film));
         xf_req.pc = px;

@@ -59,6 +59,7 @@ struct ConvVariant {
     int wg_cap = 2;   // persistent workgroups per CU (upper bound; LDS may allow fewer)
     bool lr = false;  // low-resolution kernel (kernels_lr.h): smem is the whole requirement, nothing is added per launch
     bool wr = false;  // resident-weights instantiation (kernels_conv.h MATH = 5): ONE 32-channel stage per work item -- the launch passes n_chunks = 1, CK = 32; reads w_f16
+    int nbs = 1;      // statistics partials per work item: the NB = 2 f16x2 3x3 tilings (cfg 67 / 68) write one per 32-cout block, as the 32-cout tilings they replace do
     const char* name = "";
 };
 // operand format of a split-operand conv: what get_conv_variant / get_lr_variant instantiate and which weight pack the launch reads

@@ -37,6 +37,21 @@ ConvVariant get_xf_variant(int stride, int pro, int cfg, int vec, int epi, int n
         if (cfg == 27) return xf1<1, 16, 16, 16, 8, PRO_NONE, 2, EPI_XF1, 3>("conv3x3_cat_xfilm");
         if (cfg == 28) return xf1<1, 8, 16, 16, 4, PRO_NONE, 2, EPI_XF1, 3>("conv3x3_cat_xfilm");
     }
+    if (stride == 1 && pro == PRO_GN_SILU && vec == 1 && epi == EPI_RES && nbx == 2 && cfg == 68) {
+        // ResnetBlock.block2 with 64 couts as ONE 64-cout item per pixel tile (conv_variants.h cfg 68) -> next block's x_conv 64 -> 64 (round 7).  Only the four-wave
+        // 8 x 16 form: the eight-wave one has no registers left for it (conv_variants.h).
+        ConvVariant v;
+        v.fn = conv_mfma_kernel<3, 1, 0, 8, 16, 16, 4, 1, 1, 2, PRO_GN_SILU, 1, EPI_RES | EPI_XF2, 0, 3>;
+        v.smem = conv_smem_bytes<3, 1, 0, 8, 16, 16, 2, PRO_GN_SILU, 4, 3, 2>() + XF64_LDS_BYTES;
+        v.th = 8;
+        v.tw = 16;
+        v.nt = 64;
+        v.nthr = 256;
+        v.x3 = v.f16 = true;
+        v.nbs = 2;
+        v.name = "conv3x3_gn_silu_res_xfilm64";
+        return v;
+    }
     if (stride == 2 && pro == PRO_NONE && vec == 1 && epi == 0 && nbx == 2) {  // Downsample 32 -> 32 -> next block's x_conv 32 -> 64
         if (cfg == 28) return xf1<2, 8, 16, 16, 4, PRO_NONE, 1, EPI_XF2, 3>("conv3x3_s2_xfilm");
     }

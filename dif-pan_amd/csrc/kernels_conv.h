@@ -188,8 +188,19 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
     static_assert(!PRED || SAMP, "prediction conversion: sampler epilogue only");
     constexpr int NBX = (EPI & EPI_XF1) ? 1 : ((EPI & EPI_XF2) ? 2 : 0);  // 32-cout blocks of the folded x_conv
     constexpr bool XF = NBX > 0;
+    // Round 7: the f16x2 3x3 tilings with NB = 2 (64-cout work items) keep the GroupNorm partials of the 32-cout items they replace: one {sum, sum^2} per 32-cout
+    // BLOCK of the item, each summed exactly as a 32-cout item sums its tile and written to the index that item writes.  Conv outputs are bit-identical (same products,
+    // same K order per pixel and cout), so the consumer reads the same partial array either way and the host may pick NB by the item count.  (The 1x1 tilings with
+    // NB > 1 and the exact-fp32 tiling 6 keep one partial per item.)
+    constexpr bool SPLIT = KS == 3 && NB > 1 && MATH == 3;
+    constexpr int NBS = SPLIT ? NB : 1;                                   // statistics partials per work item (and half tile)
     static_assert(!SAMP || (!SOUT && !RES && !FILM), "sampler epilogue: the plain vector epilogue of the final conv");
-    static_assert(!XF || (MB == 1 && NB == 1 && WN == 1 && !SOUT && !SAMP && !FILM && !SILU && PRO != PRO_GN_DW), "x_conv + FiLM fold: one wave holds all 32 couts of its pixels");
+    static_assert(!XF || (MB == 1 && (NB == 1 || (SPLIT && NB == 2 && NBX == 2)) && WN == 1 && !SOUT && !SAMP && !FILM && !SILU && PRO != PRO_GN_DW),
+                  "x_conv + FiLM fold: one wave holds all couts of its pixels (32, or 64 as the two blocks of an NB = 2 item)");
+    // XF on an NB = 2 item (round 7): K = 64 = the item's two 32-cout blocks, 64 -> 64 x_conv.  The A fragments (64 floats per lane) do not fit beside the two
+    // stage register sets: they live in LDS as [K half][32-cout block][quad][lane][4] (conflict-free ds_read_b128) and are read in the epilogue only.
+    constexpr bool XFL = XF && NB == 2;
+    constexpr int XWL = XFL ? NB * NBX * 1024 : 0;  // floats
     static_assert(!DWM || (KS == 1 && STRIDE == 1 && !UPS && VEC == 1), "depthwise staging is for plain 1x1 convs");
     static_assert(PRO != PRO_COLSM || VEC == 1, "column-softmax prologue needs uniform-source float4 staging");
     constexpr int LPAD = DWM ? 1 : PAD;
@@ -218,13 +229,14 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
     DDIF_DYN_SMEM(smem);
     float* As = reinterpret_cast<float*>(smem);   // [2][ABUF]  input halo tile of one channel chunk
     float* Ws = As + 2 * ABUF;                    // [NWB][WBUF]  weight chunk in B-fragment order
-    double* red = reinterpret_cast<double*>(smem + (size_t)(2 * ABUF + NWB * WBUF) * sizeof(float));  // [2][2 * NW]
-    float* Hs = reinterpret_cast<float*>(smem + (size_t)(2 * ABUF + NWB * WBUF) * sizeof(float) + 4 * NW * sizeof(double));  // [HBUF]
+    double* red = reinterpret_cast<double*>(smem + (size_t)(2 * ABUF + NWB * WBUF) * sizeof(float));  // [2][NBS][2 * NW]
+    float* Hs = reinterpret_cast<float*>(smem + (size_t)(2 * ABUF + NWB * WBUF) * sizeof(float) + 4 * NW * NBS * sizeof(double));  // [HBUF]
     float* DWs = Hs + HBUF;                       // [9][Ctot]
     [[maybe_unused]] double* redx = reinterpret_cast<double*>(DWs + DWMAX);  // XF: [2][2 * NW] partials of the second output
     float* GBs = DWs + DWMAX + (XF ? 8 * NW : 0); // GroupNorm gamma | beta, [2][n_chunks * CK] (host adds the bytes)
     float* BTs = GBs + (GNP ? 2 * a.n_chunks * CK : 0);  // bias (+ the step's time-bias row) of all n_ct * NT couts
     [[maybe_unused]] float* BXs = BTs + a.n_ct * (32 * NB * WN);  // XF: x_conv bias [32 * NBX]
+    [[maybe_unused]] float* XWs = BXs + 32 * NBX;                 // XFL: x_conv A fragments [XWL] (conv_smem_extra: xf_cin = 64)
 
     const int tid = threadIdx.x, lane = tid & 63;
 #ifdef DDIF_EMU
@@ -288,8 +300,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
         }
     }
     // XF: this lane's A fragments of the register GEMM, resident for the whole launch: step s = 4g + i contracts cout 8g + 4h + i (k = h); lane (j, h) supplies W_x[32 nx + j][that cout]
-    [[maybe_unused]] float xw[XF ? NBX : 1][16];
-    if constexpr (XF) {
+    [[maybe_unused]] float xw[(XF && !XFL) ? NBX : 1][16];
+    if constexpr (XF && !XFL) {
 #pragma unroll
         for (int nx = 0; nx < NBX; ++nx)
 #pragma unroll
@@ -623,45 +635,52 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
         if (a.st_out && pend && tid == 0) {
             const Pos p = pend_pos;
             const int t = (p.oy0 / TH) * a.tiles_x + p.ox0 / TW;
-            const double* r = red + pend_par * 2 * NW;
-            if (NW == 8 && TH == 16 && a.st_halves) {
-                // one partial per 8 x 16 half tile: waves 0-3 = rows 0-7, waves 4-7 = rows 8-15, each summed as the four-wave tiling sums its tile
-                const int ty = p.oy0 / TH, tx = p.ox0 / TW;
-                const size_t np8 = (size_t)a.tiles_x * a.tiles_y8 * a.n_ct;
+            const int nblk = a.n_ct * NBS;  // 32-cout blocks with a partial of their own (SPLIT), else the cout tiles
 #pragma unroll
-                for (int hf = 0; hf < 2; ++hf) {
-                    const int ty8 = 2 * ty + hf;
-                    if (ty8 < a.tiles_y8) {  // (a bottom half below the image has no tile in the 8 x 16 tiling)
-                        const size_t pi = ((size_t)p.b * np8 + ((size_t)ty8 * a.tiles_x + tx) * a.n_ct + p.ct) * 2;
-                        const double* q = r + 8 * hf;
-                        a.st_out[pi + 0] = (q[0] + q[2]) + (q[4] + q[6]);
-                        a.st_out[pi + 1] = (q[1] + q[3]) + (q[5] + q[7]);
-                        if constexpr (XF) {
-                            const double* qx = redx + pend_par * 2 * NW + 8 * hf;
-                            a.xf_st[pi + 0] = (qx[0] + qx[2]) + (qx[4] + qx[6]);
-                            a.xf_st[pi + 1] = (qx[1] + qx[3]) + (qx[5] + qx[7]);
+            for (int ns = 0; ns < NBS; ++ns) {
+                const double* r = red + (pend_par * NBS + ns) * 2 * NW;
+                const int cb = p.ct * NBS + ns;
+                if (NW == 8 && TH == 16 && a.st_halves) {
+                    // one partial per 8 x 16 half tile: waves 0-3 = rows 0-7, waves 4-7 = rows 8-15, each summed as the four-wave tiling sums its tile
+                    const int ty = p.oy0 / TH, tx = p.ox0 / TW;
+                    const size_t np8 = (size_t)a.tiles_x * a.tiles_y8 * nblk;
+#pragma unroll
+                    for (int hf = 0; hf < 2; ++hf) {
+                        const int ty8 = 2 * ty + hf;
+                        if (ty8 < a.tiles_y8) {  // (a bottom half below the image has no tile in the 8 x 16 tiling)
+                            const size_t pi = ((size_t)p.b * np8 + ((size_t)ty8 * a.tiles_x + tx) * nblk + cb) * 2;
+                            const double* q = r + 8 * hf;
+                            a.st_out[pi + 0] = (q[0] + q[2]) + (q[4] + q[6]);
+                            a.st_out[pi + 1] = (q[1] + q[3]) + (q[5] + q[7]);
+                            if constexpr (XF) {  // (n_ct = 1: the second output has ONE partial per half tile, at pi / NBS)
+                                if (ns == 0) {
+                                    const double* qx = redx + pend_par * 2 * NW + 8 * hf;
+                                    a.xf_st[pi / NBS + 0] = (qx[0] + qx[2]) + (qx[4] + qx[6]);
+                                    a.xf_st[pi / NBS + 1] = (qx[1] + qx[3]) + (qx[5] + qx[7]);
+                                }
+                            }
                         }
                     }
+                } else {
+                    const size_t pi = ((size_t)p.b * (tiles * nblk) + (size_t)t * nblk + cb) * 2;
+                    double t0 = (r[0] + r[2]) + (r[4] + r[6]), t1 = (r[1] + r[3]) + (r[5] + r[7]);
+                    if (NW == 8) {
+                        t0 += (r[8] + r[10]) + (r[12] + r[14]);
+                        t1 += (r[9] + r[11]) + (r[13] + r[15]);
+                    }
+                    a.st_out[pi + 0] = t0;
+                    a.st_out[pi + 1] = t1;
+                    if constexpr (XF) if (ns == 0) {  // the second output's partial of the same item (n_ct = 1): one per tile, at pi / NBS
+                        const double* rx = redx + pend_par * 2 * NW;
+                        double u0 = (rx[0] + rx[2]) + (rx[4] + rx[6]), u1 = (rx[1] + rx[3]) + (rx[5] + rx[7]);
+                        if (NW == 8) {
+                            u0 += (rx[8] + rx[10]) + (rx[12] + rx[14]);
+                            u1 += (rx[9] + rx[11]) + (rx[13] + rx[15]);
+                        }
+                        a.xf_st[pi / NBS + 0] = u0;
+                        a.xf_st[pi / NBS + 1] = u1;
+                    }
                 }
-            } else {
-            const size_t pi = ((size_t)p.b * (tiles * a.n_ct) + (size_t)t * a.n_ct + p.ct) * 2;
-            double t0 = (r[0] + r[2]) + (r[4] + r[6]), t1 = (r[1] + r[3]) + (r[5] + r[7]);
-            if (NW == 8) {
-                t0 += (r[8] + r[10]) + (r[12] + r[14]);
-                t1 += (r[9] + r[11]) + (r[13] + r[15]);
-            }
-            a.st_out[pi + 0] = t0;
-            a.st_out[pi + 1] = t1;
-            if constexpr (XF) {  // the second output's partial of the same item (n_ct = 1)
-                const double* rx = redx + pend_par * 2 * NW;
-                double u0 = (rx[0] + rx[2]) + (rx[4] + rx[6]), u1 = (rx[1] + rx[3]) + (rx[5] + rx[7]);
-                if (NW == 8) {
-                    u0 += (rx[8] + rx[10]) + (rx[12] + rx[14]);
-                    u1 += (rx[9] + rx[11]) + (rx[13] + rx[15]);
-                }
-                a.xf_st[pi + 0] = u0;
-                a.xf_st[pi + 1] = u1;
-            }
             }
         }
         pend = false;
@@ -701,6 +720,20 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
         unsigned e_po[MB], e_pf[MB];  // this item's byte offsets (clamped to the tile origin for pixels outside the image)
         bool e_pok[MB];
         size_t tile_el = 0;           // element index of (tile origin pixel, first cout of this wave)
+        // XF: scale | shift of the second output at this lane's pixel, issued with the other epilogue operands ahead of the MFMAs (XFL: 64 registers across the MFMA
+        // loop -- the four-wave form has them, 256 VGPRs + 205 AGPRs and no scratch)
+        [[maybe_unused]] auto xf_loads = [&]() {
+            const char* xfb = reinterpret_cast<const char*>(a.xf_film + (size_t)((Cp.b * a.Hout + Cp.oy0) * a.Wout + Cp.ox0) * 2 * (32 * NBX));
+            const unsigned pf = e_pok[0] ? e_xfoff[0] : (unsigned)(16 * h);
+            e_pxo = e_pok[0] ? e_xoff[0] : (unsigned)(16 * h);
+#pragma unroll
+            for (int nx = 0; nx < NBX; ++nx)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    e_xs[nx][g] = *reinterpret_cast<const float4*>(xfb + (pf + (unsigned)((nx * 32 + 8 * g) * 4)));
+                    e_xh[nx][g] = *reinterpret_cast<const float4*>(xfb + (size_t)(32 * NBX) * 4 + (pf + (unsigned)((nx * 32 + 8 * g) * 4)));
+                }
+        };
         if constexpr (LAST) {
             full = (Cp.oy0 + TH <= a.Hout) & (Cp.ox0 + TW <= a.Wout);
             const size_t tile_pix = (size_t)((Cp.b * a.Hout + Cp.oy0) * a.Wout + Cp.ox0);
@@ -739,18 +772,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
                             }
                         }
                     }
-                if constexpr (XF) {
-                    const char* xfb = reinterpret_cast<const char*>(a.xf_film + tile_pix * 2 * (32 * NBX));
-                    const unsigned pf = e_pok[0] ? e_xfoff[0] : (unsigned)(16 * h);
-                    e_pxo = e_pok[0] ? e_xoff[0] : (unsigned)(16 * h);
-#pragma unroll
-                    for (int nx = 0; nx < NBX; ++nx)
-#pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            e_xs[nx][g] = *reinterpret_cast<const float4*>(xfb + (pf + (unsigned)((nx * 32 + 8 * g) * 4)));
-                            e_xh[nx][g] = *reinterpret_cast<const float4*>(xfb + (size_t)(32 * NBX) * 4 + (pf + (unsigned)((nx * 32 + 8 * g) * 4)));
-                        }
-                }
+                if constexpr (XF) xf_loads();
             }
         }
         // (2) prefetch stage +2
@@ -874,13 +896,15 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
         if constexpr (LAST) {
             // (4) epilogue of work item Cp: lane (j, h) owns pixel j of each 32-pixel block and, per accumulator quad g,
             //     the 4 consecutive couts 8g + 4h .. +3 of each 32-cout block
-            float s1 = 0.f, s2 = 0.f;
+            float s1[NBS], s2[NBS];  // SPLIT: per 32-cout block of the item
+#pragma unroll
+            for (int ns = 0; ns < NBS; ++ns) s1[ns] = s2[ns] = 0.f;
             [[maybe_unused]] float sx1 = 0.f, sx2 = 0.f;  // XF: statistics of the second output
             if constexpr (!SOUT) {
                 char* obase = reinterpret_cast<char*>(a.out + tile_el);
                 auto epi = [&](auto guard) {
                     constexpr bool GUARD = decltype(guard)::LAST;  // StageKind<1> = bounds-checked stores
-                    [[maybe_unused]] float vx[16];  // XF: the 16 output values of this lane = the B operand of the register GEMM
+                    [[maybe_unused]] float vx[XF ? NB : 1][16];  // XF: the 16 output values of this lane per 32-cout block = the B operands of the register GEMM
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
@@ -898,7 +922,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
                                     if constexpr (SILU) x = dd_silu(x);
                                     if constexpr (RES) x += (&e_res[mb][nb][g].x)[i];
                                     v[i] = x;
-                                    if constexpr (XF) vx[4 * g + i] = x;
+                                    if constexpr (XF) vx[nb][4 * g + i] = x;
                                 }
                                 if constexpr (SAMP) {
                                     if (e_pok[mb] && co < a.Cout) {
@@ -934,8 +958,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
                                     // (streaming / nontemporal stores measured slower: 1x1 64->64 @64^2 63 vs 38 us)
                                     if (!(ABL & 4) || v[0] == 12345.678f)
                                         *reinterpret_cast<float4*>(obase + (e_po[mb] + (unsigned)((nb * 32 + 8 * g) * 4))) = make_float4(v[0], v[1], v[2], v[3]);
-                                    s1 += (v[0] + v[1]) + (v[2] + v[3]);
-                                    s2 += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+                                    s1[SPLIT ? nb : 0] += (v[0] + v[1]) + (v[2] + v[3]);
+                                    s2[SPLIT ? nb : 0] += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
                                 }
                             }
                     if constexpr (XF) {
@@ -947,7 +971,20 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
 #pragma unroll
                             for (int r = 0; r < 16; ++r) c2[r] = 0.f;
 #pragma unroll
-                            for (int sx = 0; sx < 16; ++sx) c2 = DDIF_MFMA_32x32x2(xw[nx][sx], vx[sx], c2);
+                            for (int kh = 0; kh < NB; ++kh)  // K half = 32-cout block of the producer (XFL: two)
+#pragma unroll
+                                for (int q = 0; q < 4; ++q) {
+                                    float wq[4];
+                                    if constexpr (XFL) {
+                                        const float4 t = *reinterpret_cast<const float4*>(&XWs[((kh * NBX + nx) * 4 + q) * 256 + lane * 4]);
+                                        wq[0] = t.x, wq[1] = t.y, wq[2] = t.z, wq[3] = t.w;
+                                    } else {
+#pragma unroll
+                                        for (int i = 0; i < 4; ++i) wq[i] = xw[nx][4 * q + i];
+                                    }
+#pragma unroll
+                                    for (int i = 0; i < 4; ++i) c2 = DDIF_MFMA_32x32x2(wq[i], vx[kh][4 * q + i], c2);
+                                }
 #pragma unroll
                             for (int g = 0; g < 4; ++g) {
                                 const float4 bx = *reinterpret_cast<const float4*>(&BXs[nx * 32 + 8 * g + 4 * h]);
@@ -983,17 +1020,20 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
                                 if constexpr (SILU) x = dd_silu(x);
                                 if constexpr (RES) x += a.res[pix * a.Cout + co];
                                 if (!(ABL & 4) || x == 12345.678f) a.out[pix * a.Cout + co] = x;
-                                s1 += x;
-                                s2 += x * x;
+                                s1[SPLIT ? nb : 0] += x;
+                                s2[SPLIT ? nb : 0] += x * x;
                             }
                         }
             }
             if (a.st_out) {
-                const double d1 = (double)wave_sum_fast(s1), d2 = (double)wave_sum_fast(s2);  // fp32 tree in-wave, fp64 beyond
                 pend_par ^= 1;
-                if (lane == 63) {
-                    red[pend_par * 2 * NW + wave * 2 + 0] = d1;
-                    red[pend_par * 2 * NW + wave * 2 + 1] = d2;
+#pragma unroll
+                for (int ns = 0; ns < NBS; ++ns) {
+                    const double d1 = (double)wave_sum_fast(s1[ns]), d2 = (double)wave_sum_fast(s2[ns]);  // fp32 tree in-wave, fp64 beyond
+                    if (lane == 63) {
+                        red[(pend_par * NBS + ns) * 2 * NW + wave * 2 + 0] = d1;
+                        red[(pend_par * NBS + ns) * 2 * NW + wave * 2 + 1] = d2;
+                    }
                 }
                 if constexpr (XF) {
                     const double x1 = (double)wave_sum_fast(sx1), x2 = (double)wave_sum_fast(sx2);
@@ -1068,6 +1108,18 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
         if (WRI > 3) t_w3 = wld(3);
         if (WRI > 4) t_w4 = wld(4);
     }
+    // XFL: the x_conv A fragments, pack order [K half][32-cout block][lane][16] (ddif_net.cpp), on their way to LDS
+    constexpr int XWI = XFL ? XWL / 4 / NTHR : 1;
+    static_assert(!XFL || XWL % (4 * NTHR) == 0, "x_conv fragments: whole float4 items per thread");
+    static_assert(!XFL || XWI == 4, "x_conv fragments: four float4 per thread (four-wave workgroups)");
+    [[maybe_unused]] float4 t_x0, t_x1, t_x2, t_x3;  // (named registers, not an array: see t_w0 above)
+    if constexpr (XFL) {
+        const float4* xsrc = reinterpret_cast<const float4*>(a.xf_w);
+        t_x0 = xsrc[tid];
+        t_x1 = xsrc[tid + NTHR];
+        t_x2 = xsrc[tid + 2 * NTHR];
+        t_x3 = xsrc[tid + 3 * NTHR];
+    }
     if (GNP) gn_load_partials(a.st0, a.np0, a.st1, a.np1, R0.pos.b, &gp);
     // the step's time-bias row LAST: its address waits for the step counter (a dependent scalar load); issued earlier, every load behind it in program order waits too
     tbrow = a.tbias + (size_t)dd_late(stepv) * a.tb_rowstride;
@@ -1128,6 +1180,16 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
         }
         if constexpr (XF) {
             if (tid < 32 * NBX) BXs[tid] = a.xf_b[tid];
+            if constexpr (XFL) {
+                auto xst = [&](int k, const float4& v) {  // float4 f = (block * 64 + lane) * 4 + quad  ->  [block][quad][lane][4]
+                    const int f = tid + k * NTHR;
+                    *reinterpret_cast<float4*>(&XWs[(((f >> 8) * 4 + (f & 3)) * 64 + ((f >> 2) & 63)) * 4]) = v;
+                };
+                xst(0, t_x0);
+                xst(1, t_x1);
+                xst(2, t_x2);
+                xst(3, t_x3);
+            }
         }
     }
     __syncthreads();
@@ -1157,15 +1219,17 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
 }
 
 
-template <int KS, int STRIDE, int UPS, int TH, int TW, int CK, int NBT, int PRO = 0, int NW = 4, int MATH = 0>
-constexpr size_t conv_smem_bytes() {  // NBT = n-blocks (of 32 couts) per workgroup = NB * WN; + conv_smem_extra() at launch
+template <int KS, int STRIDE, int UPS, int TH, int TW, int CK, int NBT, int PRO = 0, int NW = 4, int MATH = 0, int NBS = 1>
+constexpr size_t conv_smem_bytes() {  // NBT = n-blocks (of 32 couts) per workgroup = NB * WN; NBS = statistics partials per item (kernel: SPLIT); + conv_smem_extra() at launch
     constexpr int IH = (TH - 1) * STRIDE + KS, IW = (TW - 1) * STRIDE + KS;
     constexpr size_t dw = PRO == PRO_GN_DW ? (size_t)((TH + 2) * (TW + 2) * (CK + 4) + 9 * 256) : 0;
     constexpr int npl = (MATH == 3 || MATH == 5) ? 2 : (MATH == 4 ? 1 : 3);
     constexpr int lda = MATH >= 1 ? npl * CK / 2 + 4 : CK + 4, wchunk = MATH >= 1 ? KS * KS * (CK / 16) * npl * 256 : KS * KS * (CK / 8) * 256;
     constexpr int rp = (MATH >= 1 && KS == 3 && STRIDE == 1) ? (MATH == 5 ? (64 - (IW * lda) % 64) % 64 : (npl == 2 ? 24 : (npl == 1 ? 40 : 8))) : 0;
-    return (size_t)(2 * IH * (IW * lda + rp) + ((MATH == 2 || MATH == 5) ? 1 : 2) * NBT * wchunk + dw) * sizeof(float) + 4 * NW * sizeof(double);
+    return (size_t)(2 * IH * (IW * lda + rp) + ((MATH == 2 || MATH == 5) ? 1 : 2) * NBT * wchunk + dw) * sizeof(float) + 4 * NW * NBS * sizeof(double);
 }
+// EPI_XF2 on an NB = 2 item (64 -> 64 x_conv): the A fragments of the register GEMM in LDS (kernel: XWs); part of that variant's ConvVariant::smem
+constexpr size_t XF64_LDS_BYTES = 2 * 2 * 1024 * sizeof(float);
 // GroupNorm prologues keep gamma | beta of all input channels in LDS; every kernel keeps bias (+ time bias) of all couts
 inline size_t conv_smem_extra(int pro, int n_chunks, int ck, int cout_pad, int xf_cout = 0) {
     // (xf_cout: the folded x_conv's bias + the second output's statistics partials, [2][2 * 8 waves] doubles)
