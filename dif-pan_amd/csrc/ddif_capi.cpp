@@ -288,6 +288,17 @@ int ddif_plan_forward_taps(ddif_plan_t plan, const float* x, const float* time_h
     DDIF_GUARD_END
 }
 
+// ---- test-only view of the conv variant table (include/ddif_testops.h)
+int ddif_conv_variant_table(int xf, const int* keys, int n, ddif_conv_variant_info* out) {
+    if (!keys || !out || n < 0) return ddif::fail(DDIF_ERR_INVALID, "ddif_conv_variant_table: bad argument");
+    for (int i = 0; i < n; ++i) {
+        const int* k = keys + 9 * i;
+        const ddif::ConvVariant v = xf ? ddif::get_xf_variant(k[0], k[1], k[2], k[3], k[4], k[5]) : ddif::get_conv_variant(k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7], k[8]);
+        out[i] = v.fn ? ddif_conv_variant_info{1, v.th, v.tw, v.nt, v.nthr, v.x3, v.f16, v.b1, v.wg_cap, v.lr, v.wr, v.nbs, (int64_t)v.smem, v.name} : ddif_conv_variant_info{};
+    }
+    return DDIF_OK;
+}
+
 int ddif_plan_sample_ddpm(ddif_plan_t plan, const ddif_ddpm_tables* tabs, const float* x_T, const float* noise, uint64_t seed,
                           uint64_t tile0, float clamp_lo, float clamp_hi, int do_clamp, float* out, void* stream) {
     DDIF_GUARD_BEGIN

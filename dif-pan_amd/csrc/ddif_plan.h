@@ -62,7 +62,8 @@ struct ConvVariant {
     int nbs = 1;      // statistics partials per work item: the NB = 2 f16x2 3x3 tilings (cfg 67 / 68) write one per 32-cout block, as the 32-cout tilings they replace do
     const char* name = "";
 };
-// operand format of a split-operand conv: what get_conv_variant / get_lr_variant instantiate and which weight pack the launch reads
+// operand format of a split-operand conv: what get_conv_variant / get_lr_variant instantiate and which weight pack the launch reads.  A REQUEST (0 / 1 / 2), not
+// the general kernel's MATH template value: those are KM_EXACT ... KM_F16X2_WR (kernels_conv.h, 0 - 5), which the tiling table picks per cfg number.
 enum { MATH_BF16X3 = 0, MATH_F16X2 = 1, MATH_BF16X1 = 2 };
 ConvVariant get_conv_variant(int ks, int stride, int ups, int ck, int pro, int cfg, int vec, int epi, int math = MATH_BF16X3);
 ConvVariant get_lr_variant(int ks, int mb, int pro, int epi, int math = MATH_BF16X3, bool rows = false);  // ddif_lr.cpp (rows: the whole-width staging, kernels_lr.h ROWS)

@@ -3,57 +3,34 @@
 // as a second output with its own GroupNorm partials.  One translation unit of its own so that it builds beside the main kernel family.
 // Only the f16x2 tilings the inference plans of the engine configuration pick for these producers are instantiated:
 //   the stem (cat[self_cond, x], VEC = 2), ResnetBlock.block2 (GroupNorm + SiLU prologue, + residual) and the Downsample conv (stride 2).
-#include "ddif_plan.h"
-#include "kernels_conv.h"
+#include "conv_variants.h"
 
 namespace ddif {
 
 namespace {
-template <int S, int TH, int TW, int CK, int NW, int PRO, int VEC, int EPI, int MATH>
-ConvVariant xf1(const char* name) {
-    ConvVariant v;
-    v.fn = conv_mfma_kernel<3, S, 0, TH, TW, CK, NW, 1, 1, 1, PRO, VEC, EPI, 0, MATH>;
-    v.smem = conv_smem_bytes<3, S, 0, TH, TW, CK, 1, PRO, NW, MATH>();
-    v.th = TH;
-    v.tw = TW;
-    v.nt = 32;
-    v.nthr = 64 * NW;
-    v.x3 = v.f16 = true;
-    v.wr = MATH == 5;
-    v.name = name;
-    return v;
-}
+// one fold: the f16x2 tiling TH x TW on NW waves with NB 32-cout blocks per item (conv_variants.h: 27 / 37 = 16x16 on eight, 28 / 68 = 8x16 on four)
+template <int S, int TH, int TW, int CK, int NW, int NB, int PRO, int VEC, int EPI, int MATH>
+ConvVariant xf(const char* name) { return conv_variant<3, S, 0, PRO, VEC, EPI, TH, TW, CK, NW, 1, 1, NB, MATH>(name); }
 }  // namespace
 
 // cfg: the tiling add_conv() chose for the conv WITHOUT the fold (27 = 16x16 pixels on eight waves, 28 = 8x16 on four, 37 = 27 with resident weights);
 // epi: its epilogue bits without the fold (0 or EPI_RES); nbx: 32-cout blocks of the x_conv (1 or 2).  Null fn: no such instantiation -> no fold.
 ConvVariant get_xf_variant(int stride, int pro, int cfg, int vec, int epi, int nbx) {
     if (stride == 1 && pro == PRO_GN_SILU && vec == 1 && epi == EPI_RES && nbx == 1) {  // ResnetBlock.block2 -> next block's x_conv 32 -> 32
-        if (cfg == 37) return xf1<1, 16, 16, 32, 8, PRO_GN_SILU, 1, EPI_RES | EPI_XF1, 5>("conv3x3_gn_silu_res_xfilm");
-        if (cfg == 27) return xf1<1, 16, 16, 16, 8, PRO_GN_SILU, 1, EPI_RES | EPI_XF1, 3>("conv3x3_gn_silu_res_xfilm");
-        if (cfg == 28) return xf1<1, 8, 16, 16, 4, PRO_GN_SILU, 1, EPI_RES | EPI_XF1, 3>("conv3x3_gn_silu_res_xfilm");
+        if (cfg == 37) return xf<1, 16, 16, 32, 8, 1, PRO_GN_SILU, 1, EPI_RES | EPI_XF1, KM_F16X2_WR>("conv3x3_gn_silu_res_xfilm");
+        if (cfg == 27) return xf<1, 16, 16, 16, 8, 1, PRO_GN_SILU, 1, EPI_RES | EPI_XF1, KM_F16X2>("conv3x3_gn_silu_res_xfilm");
+        if (cfg == 28) return xf<1, 8, 16, 16, 4, 1, PRO_GN_SILU, 1, EPI_RES | EPI_XF1, KM_F16X2>("conv3x3_gn_silu_res_xfilm");
     }
     if (stride == 1 && pro == PRO_NONE && vec == 2 && epi == 0 && nbx == 1) {  // stem -> first block's x_conv 32 -> 32
-        if (cfg == 27) return xf1<1, 16, 16, 16, 8, PRO_NONE, 2, EPI_XF1, 3>("conv3x3_cat_xfilm");
-        if (cfg == 28) return xf1<1, 8, 16, 16, 4, PRO_NONE, 2, EPI_XF1, 3>("conv3x3_cat_xfilm");
+        if (cfg == 27) return xf<1, 16, 16, 16, 8, 1, PRO_NONE, 2, EPI_XF1, KM_F16X2>("conv3x3_cat_xfilm");
+        if (cfg == 28) return xf<1, 8, 16, 16, 4, 1, PRO_NONE, 2, EPI_XF1, KM_F16X2>("conv3x3_cat_xfilm");
     }
-    if (stride == 1 && pro == PRO_GN_SILU && vec == 1 && epi == EPI_RES && nbx == 2 && cfg == 68) {
-        // ResnetBlock.block2 with 64 couts as ONE 64-cout item per pixel tile (conv_variants.h cfg 68) -> next block's x_conv 64 -> 64 (round 7).  Only the four-wave
-        // 8 x 16 form: the eight-wave one has no registers left for it (conv_variants.h).
-        ConvVariant v;
-        v.fn = conv_mfma_kernel<3, 1, 0, 8, 16, 16, 4, 1, 1, 2, PRO_GN_SILU, 1, EPI_RES | EPI_XF2, 0, 3>;
-        v.smem = conv_smem_bytes<3, 1, 0, 8, 16, 16, 2, PRO_GN_SILU, 4, 3, 2>() + XF64_LDS_BYTES;
-        v.th = 8;
-        v.tw = 16;
-        v.nt = 64;
-        v.nthr = 256;
-        v.x3 = v.f16 = true;
-        v.nbs = 2;
-        v.name = "conv3x3_gn_silu_res_xfilm64";
-        return v;
-    }
+    // ResnetBlock.block2 with 64 couts as ONE 64-cout item per pixel tile (conv_variants.h cfg 68) -> next block's x_conv 64 -> 64 (round 7).  Only the four-wave
+    // 8 x 16 form: the eight-wave one has no registers left for it (conv_variants.h).  Its smem includes the x_conv's A fragments (ConvGeom::XWL).
+    if (stride == 1 && pro == PRO_GN_SILU && vec == 1 && epi == EPI_RES && nbx == 2 && cfg == 68)
+        return xf<1, 8, 16, 16, 4, 2, PRO_GN_SILU, 1, EPI_RES | EPI_XF2, KM_F16X2>("conv3x3_gn_silu_res_xfilm64");
     if (stride == 2 && pro == PRO_NONE && vec == 1 && epi == 0 && nbx == 2) {  // Downsample 32 -> 32 -> next block's x_conv 32 -> 64
-        if (cfg == 28) return xf1<2, 8, 16, 16, 4, PRO_NONE, 1, EPI_XF2, 3>("conv3x3_s2_xfilm");
+        if (cfg == 28) return xf<2, 8, 16, 16, 4, 1, PRO_NONE, 1, EPI_XF2, KM_F16X2>("conv3x3_s2_xfilm");
     }
     return ConvVariant();
 }

@@ -151,92 +151,131 @@ enum { EPI_FILM = 1, EPI_SOUT = 2, EPI_RES = 4, EPI_SILU = 8, EPI_TBS = 16, EPI_
 // item (18 MFMA steps, one barrier, no weight re-staging: half the staged bytes, half the barriers, twice the tile bytes in flight per prefetch).
 // The weights are the MATH = 3 pack for 16-channel chunks read slab-major (step f = slab * 9 + tap), i.e. the products are accumulated in exactly
 // the order of MATH = 3 with CK = 16: bit-identical results.
-template <int KS, int STRIDE, int UPS, int TH, int TW, int CK, int WM, int WN, int MB, int NB, int PRO, int VEC, int EPI = 0, int ABL = 0, int MATH = 0>
-__global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
-    constexpr int NW = WM * WN, NTHR = 64 * NW;
-    constexpr int PAD = KS / 2;
-    constexpr int IH = (TH - 1) * STRIDE + KS, IW = (TW - 1) * STRIDE + KS;
-    constexpr bool X3 = MATH >= 1;   // split-operand paths (bf16x3, f16x2): 16-bit planes in LDS
-    constexpr bool F16 = MATH == 3 || MATH == 5;
-    constexpr bool WR = MATH == 5;   // weights resident in LDS for the whole launch (host: n_chunks == 1, n_ct == 1, shared weights)
-    constexpr bool B1 = MATH == 4;
-    constexpr int NPL = F16 ? 2 : (B1 ? 1 : 3); // operand planes
-    constexpr bool WSB = MATH == 2;  // ONE weight buffer (an extra barrier per stage): 69 KB of LDS -> two workgroups per CU, whose VALU
-                                     // staging and bf16 MFMAs then overlap (different pipes)
-    constexpr int NWB = (WSB || WR) ? 1 : 2;
-    constexpr int PS = CK / 2;                            // X3: floats per bf16 plane of one staged pixel (CK x 2 B)
-    constexpr int LDA = X3 ? NPL * PS + 4 : CK + 4;       // floats per staged pixel (X3: NPL planes + 16 B pad)
-    constexpr int LDH = CK + 4;                           // row of the fp32 scratch tile of the depthwise prologue
-    constexpr int TAPS = KS * KS;
-    constexpr int K8 = CK / 8;
-    constexpr int K16 = CK / 16;
-    constexpr int C4 = CK / 4;
-    constexpr int NF = X3 ? TAPS * K16 : TAPS * K8;       // MFMA steps per chunk: (tap, k8), or (tap, 16-channel slab)
+//
+// Names of the kernel's MATH values above.  The template parameter stays an int (the mangled kernel names carry the number).  NOT the host-side request
+// MATH_BF16X3 / MATH_F16X2 / MATH_BF16X1 of ddif_plan.h (0 / 1 / 2: what a plan asks get_conv_variant for); these say which instantiation computes it.
+enum { KM_EXACT = 0, KM_BF16X3 = 1, KM_BF16X3_WSB = 2, KM_F16X2 = 3, KM_BF16X1 = 4, KM_F16X2_WR = 5 };
+
+// Geometry of one instantiation of conv_mfma_kernel: wave layout, LDS layout and what the host needs to launch it.  The kernel takes its constants and carves its
+// LDS from here, the tiling table (conv_variants.h) fills a ConvVariant from here -- there is no second copy of any of these formulas.
+// LDS (floats from the start of the dynamic allocation):
+//   As [2][ABUF] | Ws [NWB][WBUF] | red [2][NBS][2 * NW] doubles | Hs [HBUF] | DWs [DWMAX] | runtime-sized tail (conv_smem_extra below) | XWs [XWL]
+// `smem` = the fixed regions (XWs included: the kernel carves it last, behind the tail, but its size is known here); the launch adds conv_smem_extra().
+template <int KS, int STRIDE, int TH, int TW, int CK, int WM, int WN, int NB, int PRO, int EPI, int MATH>
+struct ConvGeom {
+    static constexpr int NW = WM * WN, NTHR = 64 * NW;
+    static constexpr int NT = 32 * NB * WN;                      // couts of one work item (host: the cout tile)
+    static constexpr int IH = (TH - 1) * STRIDE + KS, IW = (TW - 1) * STRIDE + KS;
+    static constexpr bool X3 = MATH >= KM_BF16X3;   // split-operand paths (bf16x3, f16x2): 16-bit planes in LDS
+    static constexpr bool F16 = MATH == KM_F16X2 || MATH == KM_F16X2_WR;
+    static constexpr bool WR = MATH == KM_F16X2_WR; // weights resident in LDS for the whole launch (host: n_chunks == 1, n_ct == 1, shared weights)
+    static constexpr bool B1 = MATH == KM_BF16X1;
+    static constexpr int NPL = F16 ? 2 : (B1 ? 1 : 3);           // operand planes
+    static constexpr bool WSB = MATH == KM_BF16X3_WSB;  // ONE weight buffer (an extra barrier per stage): 69 KB of LDS -> two workgroups per CU, whose VALU
+                                                        // staging and bf16 MFMAs then overlap (different pipes)
+    static constexpr int NWB = (WSB || WR) ? 1 : 2;
+    static constexpr int PS = CK / 2;                            // X3: floats per bf16 plane of one staged pixel (CK x 2 B)
+    static constexpr int LDA = X3 ? NPL * PS + 4 : CK + 4;       // floats per staged pixel (X3: NPL planes + 16 B pad)
+    static constexpr int LDH = CK + 4;                           // row of the fp32 scratch tile of the depthwise prologue
+    static constexpr int TAPS = KS * KS;
+    static constexpr int K8 = CK / 8;
+    static constexpr int K16 = CK / 16;
+    static constexpr int C4 = CK / 4;
+    static constexpr int NF = X3 ? TAPS * K16 : TAPS * K8;       // MFMA steps per chunk: (tap, k8), or (tap, 16-channel slab)
     // row pad of the staged tile (floats): lanes 0-15 / 16-31 of an A-fragment read own consecutive pixels of two ROWS of the tile;
     // with a halo the row stride IW * LDA puts the second row on the banks of the first (2-way conflicts on every ds_read_b128 of
     // the 16-wide tile, 3-way on the 8-wide one); these pads make the reads conflict-free (bank search: DESIGN section 3)
-    constexpr int RP = (X3 && KS == 3 && STRIDE == 1) ? (WR ? (64 - (IW * LDA) % 64) % 64 : (NPL == 2 ? 24 : (NPL == 1 ? 40 : 8))) : 0;  // WR (CK = 32, 16-wide tiles): row stride = 0 mod 64 banks
-    constexpr int LDR = IW * LDA + RP;                    // floats per staged tile row
-    constexpr int ABUF = IH * LDR;                        // floats per LDS buffer
+    static constexpr int RP = (X3 && KS == 3 && STRIDE == 1) ? (WR ? (64 - (IW * LDA) % 64) % 64 : (NPL == 2 ? 24 : (NPL == 1 ? 40 : 8))) : 0;  // WR (CK = 32, 16-wide tiles): row stride = 0 mod 64 banks
+    static constexpr int LDR = IW * LDA + RP;                    // floats per staged tile row
+    static constexpr int ABUF = IH * LDR;                        // floats per LDS buffer
+    static constexpr int WCHUNK = X3 ? NF * NPL * 256 : NF * 256;  // floats per (32-cout block, chunk): X3 = NPL 16-bit planes of 1 KiB per step
+    static constexpr int WBUF = NB * WN * WCHUNK;                // floats of one weight chunk (all n-blocks of the cout tile)
     // PRO_GN_DW (1x1 conv over depthwise3x3(GroupNorm(x))): the LOAD tile has a one-pixel halo and goes to a scratch
     // LDS region; the depthwise conv turns it into the A tile of the 1x1 contraction.
-    constexpr bool DWM = (PRO == PRO_GN_DW);
+    static constexpr bool DWM = (PRO == PRO_GN_DW);
+    static constexpr int LH = DWM ? TH + 2 : IH, LW = DWM ? TW + 2 : IW;   // extent of the loaded tile
+    static constexpr int HBUF = DWM ? LH * LW * LDH : 0;                  // scratch for the normalised halo tile (fp32)
+    static constexpr int DWMAX = DWM ? 9 * 256 : 0;                       // depthwise weights of up to 256 channels
+    static constexpr int NBX = (EPI & EPI_XF1) ? 1 : ((EPI & EPI_XF2) ? 2 : 0);  // 32-cout blocks of the folded x_conv
+    static constexpr bool XF = NBX > 0;
+    // Round 7: the f16x2 3x3 tilings with NB = 2 (64-cout work items) keep the GroupNorm partials of the 32-cout items they replace: one {sum, sum^2} per 32-cout
+    // BLOCK of the item, each summed exactly as a 32-cout item sums its tile and written to the index that item writes.  Conv outputs are bit-identical (same products,
+    // same K order per pixel and cout), so the consumer reads the same partial array either way and the host may pick NB by the item count.  (The 1x1 tilings with
+    // NB > 1 and the exact-fp32 tiling 6 keep one partial per item.)
+    static constexpr bool SPLIT = KS == 3 && NB > 1 && MATH == KM_F16X2;
+    static constexpr int NBS = SPLIT ? NB : 1;                            // statistics partials per work item (and half tile)
+    // XF on an NB = 2 item (round 7): K = 64 = the item's two 32-cout blocks, 64 -> 64 x_conv.  The A fragments (64 floats per lane) do not fit beside the two
+    // stage register sets: they live in LDS as [K half][32-cout block][quad][lane][4] (conflict-free ds_read_b128) and are read in the epilogue only.
+    static constexpr bool XFL = XF && NB == 2;
+    static constexpr int XWL = XFL ? NB * NBX * 1024 : 0;  // floats
+    // offsets of the fixed regions (floats)
+    static constexpr int OFF_W = 2 * ABUF;
+    static constexpr int OFF_RED = OFF_W + NWB * WBUF;
+    static constexpr int OFF_H = OFF_RED + 2 * (4 * NW * NBS);
+    static constexpr int OFF_DW = OFF_H + HBUF;
+    static constexpr int OFF_TAIL = OFF_DW + DWMAX;
+    static constexpr size_t smem = (size_t)(OFF_TAIL + XWL) * sizeof(float);
+    static_assert(NW == 4 || NW == 8, "4 or 8 wavefronts per workgroup");
+    static_assert(CK % 8 == 0 && NTHR % C4 == 0, "chunk size");
+    static_assert(!F16 || PRO != PRO_COLSM, "f16x2: the column-softmax prologue stays on bf16x3 / fp32 (probabilities far below 2^-7)");
+    static_assert(RP == 0 || !DWM, "row pad: 3x3 tiles only");
+    static_assert(smem + 8192 <= 160 * 1024, "fixed regions + the launch extra add_conv allows (8 KiB) must fit the LDS of a CU");
+};
+// The runtime-sized tail, in the kernel's order: redx ([2][2 * NW] doubles, partials of a folded x_conv's output) | GBs (GroupNorm gamma | beta of all
+// n_chunks * ck input channels) | BTs (bias + the step's time-bias row of all cout_pad = n_ct * NT couts) | BXs (the folded x_conv's bias, xf_cout floats).
+// redx is paid for eight waves whatever NW is.
+inline size_t conv_smem_extra(int pro, int n_chunks, int ck, int cout_pad, int xf_cout = 0) {
+    return ((pro == PRO_GN || pro == PRO_GN_SILU || pro == PRO_GN_DW) ? (size_t)2 * n_chunks * ck : 0) * sizeof(float) + (size_t)cout_pad * sizeof(float) +
+           (xf_cout ? (size_t)xf_cout * sizeof(float) + 32 * sizeof(double) : 0);
+}
+// What the 64 -> 64 x_conv fold (EPI_XF2 on the NB = 2 tiling 68) adds to the LDS of the unfolded tiling: its XWs.  add_conv accepts the fold only if the two
+// variants' smem differ by exactly this.
+constexpr size_t XF64_LDS_BYTES = ConvGeom<3, 1, 8, 16, 16, 4, 1, 2, PRO_GN_SILU, EPI_RES | EPI_XF2, KM_F16X2>::XWL * sizeof(float);
+
+template <int KS, int STRIDE, int UPS, int TH, int TW, int CK, int WM, int WN, int MB, int NB, int PRO, int VEC, int EPI = 0, int ABL = 0, int MATH = 0>
+__global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
+    using G = ConvGeom<KS, STRIDE, TH, TW, CK, WM, WN, NB, PRO, EPI, MATH>;
+    constexpr int NW = G::NW, NTHR = G::NTHR, IW = G::IW, LH = G::LH, LW = G::LW;
+    constexpr int PAD = KS / 2;
+    constexpr bool X3 = G::X3, F16 = G::F16, WR = G::WR, B1 = G::B1, WSB = G::WSB, DWM = G::DWM, XF = G::XF, SPLIT = G::SPLIT, XFL = G::XFL;
+    constexpr int NPL = G::NPL, PS = G::PS, LDA = G::LDA, LDH = G::LDH, LDR = G::LDR, ABUF = G::ABUF, NBX = G::NBX, NBS = G::NBS, XWL = G::XWL;
+    constexpr int TAPS = G::TAPS, K8 = G::K8, K16 = G::K16, C4 = G::C4, NF = G::NF, WCHUNK = G::WCHUNK, WBUF = G::WBUF;
     constexpr bool GNP = (PRO == PRO_GN || PRO == PRO_GN_SILU || PRO == PRO_GN_DW);
     constexpr bool FILM = (EPI & EPI_FILM) != 0, SOUT = (EPI & EPI_SOUT) != 0, RES = (EPI & EPI_RES) != 0, SILU = (EPI & EPI_SILU) != 0, TBS = (EPI & EPI_TBS) != 0;
     constexpr bool SAMP = (EPI & EPI_SAMP) != 0;
     constexpr bool PRED = (EPI & EPI_PRED) != 0;
     static_assert(!PRED || SAMP, "prediction conversion: sampler epilogue only");
-    constexpr int NBX = (EPI & EPI_XF1) ? 1 : ((EPI & EPI_XF2) ? 2 : 0);  // 32-cout blocks of the folded x_conv
-    constexpr bool XF = NBX > 0;
-    // Round 7: the f16x2 3x3 tilings with NB = 2 (64-cout work items) keep the GroupNorm partials of the 32-cout items they replace: one {sum, sum^2} per 32-cout
-    // BLOCK of the item, each summed exactly as a 32-cout item sums its tile and written to the index that item writes.  Conv outputs are bit-identical (same products,
-    // same K order per pixel and cout), so the consumer reads the same partial array either way and the host may pick NB by the item count.  (The 1x1 tilings with
-    // NB > 1 and the exact-fp32 tiling 6 keep one partial per item.)
-    constexpr bool SPLIT = KS == 3 && NB > 1 && MATH == 3;
-    constexpr int NBS = SPLIT ? NB : 1;                                   // statistics partials per work item (and half tile)
     static_assert(!SAMP || (!SOUT && !RES && !FILM), "sampler epilogue: the plain vector epilogue of the final conv");
     static_assert(!XF || (MB == 1 && (NB == 1 || (SPLIT && NB == 2 && NBX == 2)) && WN == 1 && !SOUT && !SAMP && !FILM && !SILU && PRO != PRO_GN_DW),
                   "x_conv + FiLM fold: one wave holds all couts of its pixels (32, or 64 as the two blocks of an NB = 2 item)");
-    // XF on an NB = 2 item (round 7): K = 64 = the item's two 32-cout blocks, 64 -> 64 x_conv.  The A fragments (64 floats per lane) do not fit beside the two
-    // stage register sets: they live in LDS as [K half][32-cout block][quad][lane][4] (conflict-free ds_read_b128) and are read in the epilogue only.
-    constexpr bool XFL = XF && NB == 2;
-    constexpr int XWL = XFL ? NB * NBX * 1024 : 0;  // floats
     static_assert(!DWM || (KS == 1 && STRIDE == 1 && !UPS && VEC == 1), "depthwise staging is for plain 1x1 convs");
     static_assert(PRO != PRO_COLSM || VEC == 1, "column-softmax prologue needs uniform-source float4 staging");
     constexpr int LPAD = DWM ? 1 : PAD;
-    constexpr int LH = DWM ? TH + 2 : IH, LW = DWM ? TW + 2 : IW;   // extent of the loaded tile
-    constexpr int HBUF = DWM ? LH * LW * LDH : 0;                  // scratch for the normalised halo tile (fp32)
-    constexpr int DWMAX = DWM ? 9 * 256 : 0;                       // depthwise weights of up to 256 channels
     constexpr int DITEMS = (TH * TW * C4 + NTHR - 1) / NTHR;
     constexpr int NITEMS = (LH * LW * C4 + NTHR - 1) / NTHR;  // float4 input-staging items per thread and chunk
-    constexpr int WCHUNK = X3 ? NF * NPL * 256 : NF * 256;  // floats per (32-cout block, chunk): X3 = NPL 16-bit planes of 1 KiB per step
-    constexpr int WBUF = NB * WN * WCHUNK;                // floats of one weight chunk (all n-blocks of the cout tile)
     constexpr int WITEMS = WR ? 0 : (WBUF / 4 + NTHR - 1) / NTHR;  // float4 weight-staging items per thread and chunk (WR: none, the prologue copies them once)
     constexpr int WITEMS_A = WITEMS ? WITEMS : 1;
     constexpr int WRI = WR ? (WBUF / 4 + NTHR - 1) / NTHR : 1;  // WR: float4 items per thread of the one-time weight copy
     constexpr int DUMMY = DWM ? CK : (X3 ? NPL * PS : CK);  // pad slot of pixel 0 of the buffer the staging items go to (Hs for the
                                                           // depthwise prologue, else the A buffer): items past the end write here
-    static_assert(NW == 4 || NW == 8, "4 or 8 wavefronts per workgroup");
     static_assert(!X3 || (CK % 16 == 0 && (VEC == 1 || (VEC == 2 && F16 && PRO == PRO_NONE))), "split-operand paths: 16-channel slabs, float4 staging (per-thread source select: the stem on f16x2)");
     static_assert(TH * TW == 32 * MB * WM, "pixel tile must match the wave layout");
-    static_assert(CK % 8 == 0 && NTHR % C4 == 0, "chunk size");
     static_assert(NITEMS <= 32, "valid mask is 32 bits");
-    static_assert(!F16 || PRO != PRO_COLSM, "f16x2: the column-softmax prologue stays on bf16x3 / fp32 (probabilities far below 2^-7)");
-    static_assert(RP == 0 || !DWM, "row pad: 3x3 tiles only");
     static_assert(!WR || (KS == 3 && STRIDE == 1 && !UPS && CK == 32 && TW == 16 && !DWM), "resident weights: plain 3x3 convs with one 32-channel stage");
 
     dd_touch_kernargs<sizeof(ConvArgs)>();  // every line of the argument block in ONE round trip (ddif_dev.h)
     DDIF_DYN_SMEM(smem);
-    float* As = reinterpret_cast<float*>(smem);   // [2][ABUF]  input halo tile of one channel chunk
-    float* Ws = As + 2 * ABUF;                    // [NWB][WBUF]  weight chunk in B-fragment order
-    double* red = reinterpret_cast<double*>(smem + (size_t)(2 * ABUF + NWB * WBUF) * sizeof(float));  // [2][NBS][2 * NW]
-    float* Hs = reinterpret_cast<float*>(smem + (size_t)(2 * ABUF + NWB * WBUF) * sizeof(float) + 4 * NW * NBS * sizeof(double));  // [HBUF]
-    float* DWs = Hs + HBUF;                       // [9][Ctot]
-    [[maybe_unused]] double* redx = reinterpret_cast<double*>(DWs + DWMAX);  // XF: [2][2 * NW] partials of the second output
-    float* GBs = DWs + DWMAX + (XF ? 8 * NW : 0); // GroupNorm gamma | beta, [2][n_chunks * CK] (host adds the bytes)
+    float* const lds = reinterpret_cast<float*>(smem);
+    float* As = lds;                              // [2][ABUF]  input halo tile of one channel chunk
+    float* Ws = lds + G::OFF_W;                   // [NWB][WBUF]  weight chunk in B-fragment order
+    double* red = reinterpret_cast<double*>(lds + G::OFF_RED);  // [2][NBS][2 * NW]
+    float* Hs = lds + G::OFF_H;                   // [HBUF]
+    float* DWs = lds + G::OFF_DW;                 // [9][Ctot]
+    [[maybe_unused]] double* redx = reinterpret_cast<double*>(lds + G::OFF_TAIL);  // XF: [2][2 * NW] partials of the second output
+    float* GBs = lds + G::OFF_TAIL + (XF ? 8 * NW : 0);  // GroupNorm gamma | beta, [2][n_chunks * CK]
     float* BTs = GBs + (GNP ? 2 * a.n_chunks * CK : 0);  // bias (+ the step's time-bias row) of all n_ct * NT couts
-    [[maybe_unused]] float* BXs = BTs + a.n_ct * (32 * NB * WN);  // XF: x_conv bias [32 * NBX]
-    [[maybe_unused]] float* XWs = BXs + 32 * NBX;                 // XFL: x_conv A fragments [XWL] (conv_smem_extra: xf_cin = 64)
+    [[maybe_unused]] float* BXs = BTs + a.n_ct * G::NT;  // XF: x_conv bias [32 * NBX]
+    [[maybe_unused]] float* XWs = BXs + 32 * NBX;        // XFL: x_conv A fragments [XWL]
 
     const int tid = threadIdx.x, lane = tid & 63;
 #ifdef DDIF_EMU
@@ -1218,23 +1257,5 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_mfma_kernel(ConvArgs a) {
     }
 }
 
-
-template <int KS, int STRIDE, int UPS, int TH, int TW, int CK, int NBT, int PRO = 0, int NW = 4, int MATH = 0, int NBS = 1>
-constexpr size_t conv_smem_bytes() {  // NBT = n-blocks (of 32 couts) per workgroup = NB * WN; NBS = statistics partials per item (kernel: SPLIT); + conv_smem_extra() at launch
-    constexpr int IH = (TH - 1) * STRIDE + KS, IW = (TW - 1) * STRIDE + KS;
-    constexpr size_t dw = PRO == PRO_GN_DW ? (size_t)((TH + 2) * (TW + 2) * (CK + 4) + 9 * 256) : 0;
-    constexpr int npl = (MATH == 3 || MATH == 5) ? 2 : (MATH == 4 ? 1 : 3);
-    constexpr int lda = MATH >= 1 ? npl * CK / 2 + 4 : CK + 4, wchunk = MATH >= 1 ? KS * KS * (CK / 16) * npl * 256 : KS * KS * (CK / 8) * 256;
-    constexpr int rp = (MATH >= 1 && KS == 3 && STRIDE == 1) ? (MATH == 5 ? (64 - (IW * lda) % 64) % 64 : (npl == 2 ? 24 : (npl == 1 ? 40 : 8))) : 0;
-    return (size_t)(2 * IH * (IW * lda + rp) + ((MATH == 2 || MATH == 5) ? 1 : 2) * NBT * wchunk + dw) * sizeof(float) + 4 * NW * NBS * sizeof(double);
-}
-// EPI_XF2 on an NB = 2 item (64 -> 64 x_conv): the A fragments of the register GEMM in LDS (kernel: XWs); part of that variant's ConvVariant::smem
-constexpr size_t XF64_LDS_BYTES = 2 * 2 * 1024 * sizeof(float);
-// GroupNorm prologues keep gamma | beta of all input channels in LDS; every kernel keeps bias (+ time bias) of all couts
-inline size_t conv_smem_extra(int pro, int n_chunks, int ck, int cout_pad, int xf_cout = 0) {
-    // (xf_cout: the folded x_conv's bias + the second output's statistics partials, [2][2 * 8 waves] doubles)
-    return ((pro == PRO_GN || pro == PRO_GN_SILU || pro == PRO_GN_DW) ? (size_t)2 * n_chunks * ck : 0) * sizeof(float) + (size_t)cout_pad * sizeof(float) +
-           (xf_cout ? (size_t)xf_cout * sizeof(float) + 32 * sizeof(double) : 0);
-}
 
 }  // namespace ddif

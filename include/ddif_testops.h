@@ -134,6 +134,18 @@ DDIF_API int ddif_plan_tap_info(ddif_plan_t plan, int index, const char** name, 
 DDIF_API int ddif_plan_forward_taps(ddif_plan_t plan, const float* x, const float* time_host, const float* self_cond, float* out, int n_taps, const int* taps,
                                     float* const* tap_out, void* stream);
 
+/* ---- the conv variant table, as the plan builder sees it (tests/test_conv_variant_table.py) ---------------------------------
+ * What the builder's lookups return for n keys; launches nothing.  xf = 0: keys[i] = (ks, stride, ups, ck, pro, cfg, vec, epi, math), the arguments of
+ * get_conv_variant (csrc/ddif_plan.h; math = its 0 / 1 / 2 request);  xf = 1: keys[i] = (stride, pro, cfg, vec, epi, nbx, 0, 0, 0), those of get_xf_variant.
+ * out[i].found = 0: no kernel for that key (the other fields are then zero / NULL); name points at a string literal of the library. */
+typedef struct ddif_conv_variant_info {
+    int found;
+    int th, tw, nt, nthr, x3, f16, b1, wg_cap, lr, wr, nbs;
+    int64_t smem;
+    const char* name;
+} ddif_conv_variant_info;
+DDIF_API int ddif_conv_variant_table(int xf, const int* keys, int n, ddif_conv_variant_info* out);
+
 #ifdef __cplusplus
 }
 #endif

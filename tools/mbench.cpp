@@ -7,10 +7,8 @@
 #include <cstring>
 #include <cmath>
 #include <algorithm>
-#include "ddif_net.h"
-#include "kernels_conv.h"
+#include "conv_variants.h"
 using namespace ddif;
-typedef void (*ConvKernelFnT)(ConvArgs);
 namespace ddif { thread_local std::string g_err; int fail(int c, const char*, ...) { return c; } }
 
 #define CK_(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
@@ -42,7 +40,8 @@ void run(const char* name, int B, int H, int W, int Cin, int Cout, int wg_per_cu
     float* dww; CK_(hipMalloc(&dww, 9 * Cin * 4)); CK_(hipMemcpy(dww, h.data(), 9 * Cin * 4, hipMemcpyHostToDevice)); a.dw_w = dww;
     float* xn; CK_(hipMalloc(&xn, nin * 4)); if (PRO == PRO_GN_DW) a.out_xn = xn;
     float* zeros; CK_(hipMalloc(&zeros, 4096)); CK_(hipMemset(zeros, 0, 4096)); a.tbias = zeros;
-    constexpr int NT = 32 * NB * WN; a.n_ct = (Cout + NT - 1) / NT;
+    const ConvVariant v = conv_variant<KS, S, U, PRO, 1, EPI, TH, TW, CKc, WM, WN, MB, NB, MATH, ABL>();  // the instantiation and its launch geometry (ConvGeom)
+    const int NT = v.nt; a.n_ct = (Cout + NT - 1) / NT;
     const int np = a.tiles_x * a.tiles_y * a.n_ct;
     CK_(hipMalloc(&st, (size_t)B * 64 * 16)); CK_(hipMalloc(&sto, (size_t)B * np * 16));
     std::vector<double> hs((size_t)B * 64 * 2); for (size_t i = 0; i < hs.size(); i += 2) { hs[i] = 10.0; hs[i + 1] = 5000.0; }
@@ -52,15 +51,14 @@ void run(const char* name, int B, int H, int W, int Cin, int Cout, int wg_per_cu
     const long nwork = (long)B * a.tiles_x * a.tiles_y * a.n_ct;
     const long cap = 256L * wg_per_cu;
     dim3 grid((unsigned)(nwork < cap ? nwork : cap));
-    ConvKernelFnT fn = conv_mfma_kernel<KS, S, U, TH, TW, CKc, WM, WN, MB, NB, PRO, 1, EPI, ABL, MATH>;
-    const size_t smem = conv_smem_bytes<KS, S, U, TH, TW, CKc, NB * WN, PRO, WM * WN, MATH>() + conv_smem_extra(PRO, n_chunks, CKc, a.n_ct * NT);
-    if (smem > 65536) CK_(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    const size_t smem = v.smem + conv_smem_extra(PRO, n_chunks, CKc, a.n_ct * NT);
+    if (smem > 65536) CK_(hipFuncSetAttribute((const void*)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     hipEvent_t e0, e1; CK_(hipEventCreate(&e0)); CK_(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(fn, grid, dim3(64 * WM * WN), smem, 0, a);
+    for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(v.fn, grid, dim3(v.nthr), smem, 0, a);
     CK_(hipDeviceSynchronize());
     const int iters = 20;
     CK_(hipEventRecord(e0, 0));
-    for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(fn, grid, dim3(64 * WM * WN), smem, 0, a);
+    for (int i = 0; i < iters; ++i) hipLaunchKernelGGL(v.fn, grid, dim3(v.nthr), smem, 0, a);
     CK_(hipEventRecord(e1, 0)); CK_(hipEventSynchronize(e1));
     float ms; CK_(hipEventElapsedTime(&ms, e0, e1));
     const double us = ms * 1e3 / iters, flop = 2.0 * B * Hout * Wout * Cout * Cin * KS * KS;
@@ -189,10 +187,10 @@ int main(int argc, char** argv) {
         CK_(hipMemcpy(st, hs.data(), hs.size() * 8, hipMemcpyHostToDevice));
         ConvArgs a{}; a.in0 = in; a.c0 = Cin; a.B = B; a.Hin = H; a.Win = W; a.Hout = H; a.Wout = W; a.Cout = Cout; a.w = w; a.n_chunks = 2; a.bias = bias; a.gamma = gamma; a.beta = beta;
         a.out = out; a.tiles_x = 4; a.tiles_y = 4; a.res = res; a.tbias = zeros; a.n_ct = 1; a.st0 = st; a.np0 = 64; a.st_out = sto;
-        ConvKernelFnT ks[4] = {conv_mfma_kernel<3, 1, 0, 16, 16, 16, 8, 1, 1, 1, PRO_GN_SILU, 1, 0, 0, 3>, conv_mfma_kernel<3, 1, 0, 16, 16, 16, 8, 1, 1, 1, PRO_GN_SILU, 1, EPI_RES, 0, 3>,
-                               conv_mfma_kernel<3, 1, 0, 16, 16, 16, 8, 1, 1, 1, PRO_NONE, 1, EPI_SILU, 0, 3>, conv_mfma_kernel<3, 1, 0, 16, 16, 16, 8, 1, 1, 1, PRO_NONE, 1, EPI_RES, 0, 3>};
-        size_t sm[4] = {conv_smem_bytes<3, 1, 0, 16, 16, 16, 1, PRO_GN_SILU, 8, 3>() + conv_smem_extra(PRO_GN_SILU, 2, 16, 32), 0, conv_smem_bytes<3, 1, 0, 16, 16, 16, 1, PRO_NONE, 8, 3>() + conv_smem_extra(PRO_NONE, 2, 16, 32), 0};
-        sm[1] = sm[0]; sm[3] = sm[2];
+        const ConvVariant vs[4] = {conv_variant<3, 1, 0, PRO_GN_SILU, 1, 0, 16, 16, 16, 8, 1, 1, 1, KM_F16X2>(), conv_variant<3, 1, 0, PRO_GN_SILU, 1, EPI_RES, 16, 16, 16, 8, 1, 1, 1, KM_F16X2>(),
+                                   conv_variant<3, 1, 0, PRO_NONE, 1, EPI_SILU, 16, 16, 16, 8, 1, 1, 1, KM_F16X2>(), conv_variant<3, 1, 0, PRO_NONE, 1, EPI_RES, 16, 16, 16, 8, 1, 1, 1, KM_F16X2>()};
+        ConvKernelFn ks[4]; size_t sm[4];
+        for (int k = 0; k < 4; ++k) { ks[k] = vs[k].fn; sm[k] = vs[k].smem + conv_smem_extra(k < 2 ? PRO_GN_SILU : PRO_NONE, 2, 16, 32); }
         for (int k = 0; k < 4; ++k) CK_(hipFuncSetAttribute((const void*)ks[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm[k]));
         hipEvent_t e0, e1; CK_(hipEventCreate(&e0)); CK_(hipEventCreate(&e1));
         auto timeseq = [&](const char* name, std::vector<int> seq) {
