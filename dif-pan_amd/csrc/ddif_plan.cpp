@@ -2335,6 +2335,144 @@ int Plan::sample_dpmpp(const ddif_dpm_tables* t, const float* xT, float lo, floa
     return 0;
 }
 
+// A host-built solver program (include/ddif.h ddif_dpm_program; reference solver/dpm_solver.py:1055-1253).  Validated as a whole before the first launch.
+int Plan::sample_dpm(const ddif_dpm_program* prog, const float* xT, float lo, float hi, int do_clamp, float* out, float* inter_out, hipStream_t s) {
+    if (!cond_set) return fail(DDIF_ERR_STATE, "ddif_plan_sample_dpm before ddif_plan_set_cond");
+    if (!prog || !prog->ops || prog->n_ops < 1 || !xT || !out) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: NULL program, op table, x_T or out");
+    if (prog->algorithm != DDIF_DPM_ALGO_DPMSOLVERPP && prog->algorithm != DDIF_DPM_ALGO_DPMSOLVER)
+        return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: algorithm %d (0 dpmsolver++, 1 dpmsolver)", prog->algorithm);
+    if (int e = check_sampler_net(net)) return e;
+    const bool dyn = thr_mode == DDIF_THRESHOLD_SOLVER;
+    if (dyn && do_clamp)
+        return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: the plan thresholds dynamically (ddif_plan_set_threshold mode 2) -- the image-space clamp is the other corrector, not an addition");
+    const int NR = DDIF_DPM_NUM_REGS;
+    auto reg_ok = [NR](int r) { return r >= 0 && r < NR; };
+    bool st_set[DDIF_DPM_NUM_REGS] = {true, false, false}, m_set[DDIF_DPM_NUM_REGS] = {false, false, false};
+    bool need_reg2 = false;
+    std::vector<float> t_model;
+    for (int k = 0; k < prog->n_ops; ++k) {
+        const ddif_dpm_op& op = prog->ops[k];
+        if (op.kind == DDIF_DPM_EVAL || op.kind == DDIF_DPM_FINAL_DENOISE) {
+            if (!reg_ok(op.src) || !reg_ok(op.dst)) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: op %d names register %d -> %d (0..%d)", k, op.src, op.dst, NR - 1);
+            if (!st_set[op.src]) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: op %d evaluates state register %d before it is written", k, op.src);
+            if (op.kind == DDIF_DPM_EVAL) m_set[op.dst] = true;
+            else st_set[op.dst] = true;
+            need_reg2 |= op.src == 2 || (op.kind == DDIF_DPM_FINAL_DENOISE && op.dst == 2);
+            t_model.push_back(op.t_model);
+        } else if (op.kind == DDIF_DPM_UPDATE) {
+            if (!reg_ok(op.src) || !reg_ok(op.dst)) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: op %d names register %d -> %d (0..%d)", k, op.src, op.dst, NR - 1);
+            if (!st_set[op.src]) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: op %d updates state register %d before it is written", k, op.src);
+            int nm = 0;
+            if (op.form == DDIF_DPM_FORM_MULTI) {
+                if (op.order < 1 || op.order > 3) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: op %d has order %d (1..3)", k, op.order);
+                nm = op.order;
+            } else if (op.form == DDIF_DPM_FORM_LIN1) nm = 1;
+            else if (op.form == DDIF_DPM_FORM_LIN2 || op.form == DDIF_DPM_FORM_TAY3) nm = 3;
+            else return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: op %d has update form %d", k, op.form);
+            for (int j = 0; j < nm; ++j) {
+                if (!reg_ok(op.m[j])) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: op %d names model register %d (0..%d)", k, op.m[j], NR - 1);
+                if (!m_set[op.m[j]]) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: op %d reads model register %d before it is written", k, op.m[j]);
+            }
+            st_set[op.dst] = true;
+            need_reg2 |= op.src == 2 || op.dst == 2;
+        } else if (op.kind == DDIF_DPM_EMIT) {
+            if (!reg_ok(op.src)) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: op %d names register %d (0..%d)", k, op.src, NR - 1);
+            if (!st_set[op.src]) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: op %d emits state register %d before it is written", k, op.src);
+            if (!inter_out) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: op %d emits an intermediate but inter_out is NULL", k);
+            need_reg2 |= op.src == 2;
+        } else {
+            return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: op %d has kind %d", k, op.kind);
+        }
+    }
+    if (t_model.empty()) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: the program evaluates the network nowhere");
+    if (side_pending) {
+        train_join(s);
+        side_pending = false;
+    }
+    const int HW = H * W;
+    const size_t n = (size_t)B * HW * C;
+    if (need_reg2 && !xreg2)
+        if (int e = dalloc(&xreg2, n)) return e;
+    float* const st[DDIF_DPM_NUM_REGS] = {img[0], img[1], xreg2};
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, ew_grid(n), dim3(256), 0, s, xT, B, C, HW, 0, C, img[0]);
+    if (int e = time_rows(t_model.data(), (int)t_model.size(), s)) return e;
+    QuantArgs qa{};
+    if (dyn) {
+        qa.a = net_out.p;
+        qa.n = (long long)HW * C;
+        qa.form = QUANT_DPM;
+        qa.pred = pred_mode;
+        quantile_rank(thr_ratio, qa.n, &qa.k_lo, &qa.k_hi, &qa.w);
+        qa.max_val = thr_max;
+        qa.s_out = d_thr;
+    }
+    auto set_update = [&](DpmEvalArgs& a, const ddif_dpm_op& u) {
+        a.form = u.form == DDIF_DPM_FORM_MULTI ? DPM_FORM_MULTI : u.form == DDIF_DPM_FORM_TAY3 ? DPM_FORM_TAY3 : DPM_FORM_LIN2;
+        a.order = u.order;
+        a.x = st[u.src];
+        a.out = st[u.dst];
+        const int nm = u.form == DDIF_DPM_FORM_MULTI ? u.order : u.form == DDIF_DPM_FORM_LIN1 ? 1 : 3;
+        a.m0 = mbuf[u.m[0]];
+        a.m1 = nm >= 2 ? mbuf[u.m[1]] : nullptr;
+        a.m2 = nm >= 3 ? mbuf[u.m[2]] : nullptr;
+        for (int j = 0; j < 9; ++j) a.c[j] = u.c[j];
+    };
+    int row = 0, emitted = 0;
+    for (int k = 0; k < prog->n_ops; ++k) {
+        const ddif_dpm_op& op = prog->ops[k];
+        if (op.kind == DDIF_DPM_EMIT) {
+            hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid(n), dim3(256), 0, s, (const float*)st[op.src], B, C, HW, inter_out + (size_t)emitted * n);
+            ++emitted;
+            continue;
+        }
+        DpmEvalArgs a{};
+        a.n = n;
+        a.per = (size_t)HW * C;
+        if (op.kind == DDIF_DPM_UPDATE) {  // an update on its own (the program did not put it behind an evaluation)
+            set_update(a, op);
+            hipLaunchKernelGGL(dpm_eval_update_kernel, ew_grid(n), dim3(256), 0, s, a);
+            continue;
+        }
+        const bool fin = op.kind == DDIF_DPM_FINAL_DENOISE;
+        const bool data = fin || prog->algorithm == DDIF_DPM_ALGO_DPMSOLVERPP;  // the final denoise is the data prediction with its corrector under either algorithm (:549-553)
+        StepCtx ctx;
+        ctx.x = ctx.sc = st[op.src];  // model_wrapper never passes self_cond (dpm_solver.py:295) -> x
+        ctx.tb = tb + (size_t)row * net->nslots;
+        const bool prof = prof_every > 0 && (row % prof_every) == 0;
+        ++row;
+        run_prog(step, s, ctx, prof);
+        if (dyn && data) {  // s_b of this evaluation's x0 (solver/dpm_solver.py:424-433), on the device
+            QuantArgs q = qa;
+            q.xt = st[op.src];
+            q.alpha = op.alpha;
+            q.sigma = op.sigma;
+            quantile_launch(q, B, s);
+        }
+        a.net = net_out.p;
+        a.xe = st[op.src];
+        a.lms = lms.p;
+        a.thr = (dyn && data) ? d_thr : nullptr;
+        a.alpha = op.alpha;
+        a.sigma = op.sigma;
+        a.lo = lo;
+        a.hi = hi;
+        a.do_clamp = data ? do_clamp : 0;
+        a.model_type = pred_mode;
+        a.eps_only = data ? 0 : 1;
+        a.form = DPM_FORM_NONE;
+        if (fin) {
+            a.out = st[op.dst];
+        } else {
+            a.m_out = mbuf[op.dst];
+            if (k + 1 < prog->n_ops && prog->ops[k + 1].kind == DDIF_DPM_UPDATE) set_update(a, prog->ops[++k]);  // the update behind this evaluation rides in its launch
+        }
+        hipLaunchKernelGGL(dpm_eval_update_kernel, ew_grid(n), dim3(256), 0, s, a);
+    }
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid(n), dim3(256), 0, s, (const float*)img[0], B, C, HW, out);
+    DDIF_HIPCHK(hipGetLastError());
+    return 0;
+}
+
 int Plan::q_sample_forward(const float* x0, const float* noise, const float* a_h, const float* s_h, const float* t_h,
                            const float* sc, float* pred, hipStream_t s, const ddif_objective_rows* rows, float* recon_out) {
     if (!cond_set) return fail(DDIF_ERR_STATE, "ddif_plan_q_sample_forward before ddif_plan_set_cond");
@@ -2367,3 +2505,47 @@ int Plan::q_sample_forward(const float* x0, const float* noise, const float* a_h
 }
 
 }  // namespace ddif
+
+// TEST-ONLY (include/ddif_testops.h): one launch of dpm_eval_update_kernel on plain arrays
+extern "C" int ddif_dpm_eval_update(const float* net, const float* xe, const float* lms, const float* thr, int64_t n, int64_t per, float alpha, float sigma, float lo, float hi,
+                                    int do_clamp, int model_type, int algorithm, int form, int order, const float* x, const float* m0, const float* m1, const float* m2,
+                                    const float* c_host, float* m_out, float* out, void* stream) {
+    using namespace ddif;
+    if (n < 1 || per < 1 || (net && !xe) || (net && do_clamp && !lms) || model_type < 0 || model_type > 2 || (!net && !form))
+        return fail(DDIF_ERR_INVALID, "ddif_dpm_eval_update: bad argument");
+    if (form && (!x || !out || !c_host || (form != DDIF_DPM_FORM_MULTI && form != DDIF_DPM_FORM_LIN1 && form != DDIF_DPM_FORM_LIN2 && form != DDIF_DPM_FORM_TAY3) ||
+                 (form == DDIF_DPM_FORM_MULTI && (order < 1 || order > 3))))
+        return fail(DDIF_ERR_INVALID, "ddif_dpm_eval_update: bad update");
+    const int nm = !form ? 0 : form == DDIF_DPM_FORM_MULTI ? order : form == DDIF_DPM_FORM_LIN1 ? 1 : 3;
+    const float* m[3] = {m0, m1, m2};
+    for (int j = 0; j < nm; ++j) {
+        if (!m[j]) m[j] = (net && m_out) ? m_out : nullptr;  // NULL names the value of this launch
+        if (!m[j]) return fail(DDIF_ERR_INVALID, "ddif_dpm_eval_update: model value %d is missing", j);
+    }
+    DpmEvalArgs a{};
+    a.net = net;
+    a.xe = xe;
+    a.lms = lms;
+    a.thr = thr;
+    a.m_out = m_out;
+    a.alpha = alpha;
+    a.sigma = sigma;
+    a.lo = lo;
+    a.hi = hi;
+    a.do_clamp = do_clamp;
+    a.model_type = model_type;
+    a.eps_only = algorithm == DDIF_DPM_ALGO_DPMSOLVER;
+    a.n = (size_t)n;
+    a.per = (size_t)per;
+    a.form = !form ? DPM_FORM_NONE : form == DDIF_DPM_FORM_MULTI ? DPM_FORM_MULTI : form == DDIF_DPM_FORM_TAY3 ? DPM_FORM_TAY3 : DPM_FORM_LIN2;
+    a.order = order;
+    a.x = x;
+    a.m0 = nm >= 1 ? m[0] : nullptr;
+    a.m1 = nm >= 2 ? m[1] : nullptr;
+    a.m2 = nm >= 3 ? m[2] : nullptr;
+    a.out = out;
+    if (form) for (int j = 0; j < 9; ++j) a.c[j] = c_host[j];
+    hipLaunchKernelGGL(dpm_eval_update_kernel, ew_grid((size_t)n), dim3(256), 0, (hipStream_t)stream, a);
+    DDIF_HIPCHK(hipGetLastError());
+    return DDIF_OK;
+}

@@ -195,6 +195,7 @@ struct Plan {
     float* zeros = nullptr;     // 4 KiB of 0.0f: stands in for absent conv biases / time-bias rows
     float* img[2] = {nullptr, nullptr};
     float* mbuf[3] = {nullptr, nullptr, nullptr};
+    float* xreg2 = nullptr;           // third state register of the solver programs (x_s2), allocated by the first ddif_plan_sample_dpm that names it
     float* io_nchw = nullptr;         // scratch (B,C,H,W)
     float* tvals = nullptr;           // device time values
     float* tb = nullptr;              // time-bias table
@@ -339,6 +340,7 @@ struct Plan {
                     float lo, float hi, int do_clamp, float* out, hipStream_t s);
     int sample_dpmpp(const ddif_dpm_tables* t, const float* xT, float lo, float hi, int do_clamp, float* out,
                      hipStream_t s);
+    int sample_dpm(const ddif_dpm_program* prog, const float* xT, float lo, float hi, int do_clamp, float* out, float* inter_out, hipStream_t s);
     int q_sample_forward(const float* x0, const float* noise, const float* a_h, const float* s_h, const float* t_h,
                          const float* sc, float* pred, hipStream_t s, const ddif_objective_rows* rows = nullptr, float* recon_out = nullptr);
 };

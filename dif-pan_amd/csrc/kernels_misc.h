@@ -908,6 +908,103 @@ __global__ void dpm_update_kernel(DpmUpdArgs a) {
     }
 }
 
+// One launch per model evaluation of the solver programs (ddif_plan_sample_dpm): the model value of dpm_x0_kernel or, under algorithm_type="dpmsolver",
+// the noise prediction alone (solver/dpm_solver.py:435-439 over model_wrapper :296-303; no corrector there: the reference corrects inside data_prediction_fn
+// only), its store, and the update that follows it -- the same expressions in the same order as the two kernels above run one after the other, contraction off.
+//   form 0 none  (the evaluation alone; the final denoise :549-553 writes its data prediction to `out`)
+//   form 1 multi (dpm_update_kernel's expressions, orders 1..3 in c[0..7] = cx, a1, inv_r0, inv_r1, r0_frac, inv_r01, a2, a3)
+//   form 2 lin2  v = (c0*x - c1*m0) + c2*(c3*(m1 - m2))     singlestep x_s1 (c2 = 0), x_s2 (:736-740, 775-779), second-order x_t (:644-654, 667-677), third-order
+//                                                          dpmsolver x_t (:743-747, 782-786) with c3 = 1 (exact), multistep Taylor (:841-845, 855-859) with c3 = 1/r0
+//   form 3 tay3  D1_0 = c3*(m1 - m0); D1_1 = c4*(m2 - m0); D1 = (c6*D1_0 - c5*D1_1)/c7; D2 = 2*(D1_1 - D1_0)/c7; v = ((c0*x - c1*m0) + c2*D1) - c[8]*D2   (:749-758, 788-797)
+//                c3 = 1/r1, c4 = 1/r2, c5 = r1, c6 = r2, c7 = r2 - r1: true divisions, as the reference divides tensors
+// A leading minus of the reference is folded into the scalar (a - c*d and a + (-c)*d round alike).  m0 / m1 / m2 equal to m_out name the value of this launch.
+enum { DPM_FORM_NONE = 0, DPM_FORM_MULTI = 1, DPM_FORM_LIN2 = 2, DPM_FORM_TAY3 = 3 };
+struct DpmEvalArgs {
+    const float* net;   // network output; null = no evaluation in this launch (an update on its own)
+    const float* xe;    // the iterate the network saw
+    const float* lms;
+    const float* thr;   // per-sample s_b of quantile_abs_kernel, or null
+    float* m_out;       // the model value's register (null with form 0 under data prediction when only `out` is wanted)
+    float alpha, sigma, lo, hi;
+    int do_clamp, model_type, eps_only;
+    size_t n, per;
+    int form, order;
+    const float* x;     // the update's base iterate
+    const float* m0;
+    const float* m1;
+    const float* m2;
+    float* out;         // the update's result (in place over x is fine: elementwise)
+    float c[9];
+};
+__device__ __forceinline__ float dpm_model_value(const DpmEvalArgs& a, size_t i) {
+#pragma clang fp contract(off)
+    const float xv = a.xe[i], o = a.net[i];
+    float eps;
+    if (a.model_type == 0) eps = (xv - a.alpha * o) / a.sigma;
+    else if (a.model_type == 1) eps = o;
+    else {
+        const float p = a.alpha * o, q = a.sigma * xv;
+        eps = p + q;
+    }
+    if (a.eps_only) return eps;
+    float x0 = (xv - a.sigma * eps) / a.alpha;
+    if (a.do_clamp) {
+        const float l = a.lms[i];
+        x0 = fminf(fmaxf(x0 + l, a.lo), a.hi) - l;
+    } else if (a.thr) {
+        const float sb = a.thr[i / a.per];
+        x0 = fminf(fmaxf(x0, -sb), sb) / sb;
+    }
+    return x0;
+}
+__global__ void dpm_eval_update_kernel(DpmEvalArgs a) {
+#pragma clang fp contract(off)
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (size_t)gridDim.x * blockDim.x) {
+        float mv = 0.f;
+        if (a.net) {
+            mv = dpm_model_value(a, i);
+            if (a.m_out) a.m_out[i] = mv;
+        }
+        if (a.form == DPM_FORM_NONE) {
+            if (a.out) a.out[i] = mv;
+            continue;
+        }
+        const bool fresh = a.net != nullptr && a.m_out != nullptr;
+        const float x = a.x[i];
+        const float m0 = (fresh && a.m0 == a.m_out) ? mv : a.m0[i];
+        float v = a.c[0] * x - a.c[1] * m0;
+        if (a.form == DPM_FORM_MULTI) {
+            if (a.order == 2) {
+                const float m1 = (fresh && a.m1 == a.m_out) ? mv : a.m1[i];
+                const float d1 = a.c[2] * (m0 - m1);
+                v = v - (0.5f * a.c[1]) * d1;
+            } else if (a.order == 3) {
+                const float m1 = (fresh && a.m1 == a.m_out) ? mv : a.m1[i];
+                const float m2 = (fresh && a.m2 == a.m_out) ? mv : a.m2[i];
+                const float d10 = a.c[2] * (m0 - m1), d11 = a.c[3] * (m1 - m2);
+                const float d1 = d10 + a.c[4] * (d10 - d11);
+                const float d2 = a.c[5] * (d10 - d11);
+                v = (v + a.c[6] * d1) - a.c[7] * d2;
+            }
+        } else if (a.form == DPM_FORM_LIN2) {
+            if (a.m1) {  // (null: the first-order form c0*x - c1*m0 on its own)
+                const float m1 = (fresh && a.m1 == a.m_out) ? mv : a.m1[i];
+                const float m2 = (fresh && a.m2 == a.m_out) ? mv : a.m2[i];
+                const float d = a.c[3] * (m1 - m2);
+                v = v + a.c[2] * d;
+            }
+        } else {
+            const float m1 = (fresh && a.m1 == a.m_out) ? mv : a.m1[i];
+            const float m2 = (fresh && a.m2 == a.m_out) ? mv : a.m2[i];
+            const float d10 = a.c[3] * (m1 - m0), d11 = a.c[4] * (m2 - m0);
+            const float d1 = (a.c[6] * d10 - a.c[5] * d11) / a.c[7];
+            const float d2 = (2.f * (d11 - d10)) / a.c[7];
+            v = (v + a.c[2] * d1) - a.c[8] * d2;
+        }
+        a.out[i] = v;
+    }
+}
+
 // x0 from a prediction, per-sample coefficients (p_losses :708-713 self-conditioning pass, :724 / :735 recon_x0): out = cx[b]*x_t - co[b]*o, NHWC in,
 // NCHW out when `nchw` (the boundary layout) else NHWC
 __global__ void recon_x0_kernel(const float* xt, const float* o, const float* cx, const float* co, int B, int C, int HW, int nchw, float* out) {

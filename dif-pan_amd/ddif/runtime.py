@@ -51,6 +51,20 @@ class DpmTables(C.Structure):
                 ("inv_r01", _FP), ("a_phi2", _FP), ("a_phi3", _FP)]
 
 
+class DpmOp(C.Structure):  # include/ddif.h ddif_dpm_op
+    _fields_ = [("kind", C.c_int32), ("form", C.c_int32), ("order", C.c_int32), ("src", C.c_int32), ("dst", C.c_int32), ("m", C.c_int32 * 3),
+                ("t_model", C.c_float), ("alpha", C.c_float), ("sigma", C.c_float), ("c", C.c_float * 9)]
+
+
+class DpmProgram(C.Structure):
+    _fields_ = [("n_ops", C.c_int32), ("algorithm", C.c_int32), ("ops", C.POINTER(DpmOp))]
+
+
+DPM_ALGORITHMS = {"dpmsolver++": 0, "dpmsolver": 1}  # include/ddif.h DDIF_DPM_ALGO_*
+DPM_OP_KINDS = {"eval": 0, "update": 1, "final": 2, "emit": 3}  # DDIF_DPM_EVAL ..
+DPM_FORMS = {"multi": 1, "lin2": 2, "tay3": 3, "lin1": 4}  # DDIF_DPM_FORM_*
+
+
 class PredTables(C.Structure):
     _fields_ = [("n_steps", C.c_int32), ("coef_xt", _FP), ("coef_out", _FP)]
 
@@ -117,6 +131,7 @@ class _Lib:
         d.ddif_plan_sample_ddpm.argtypes = [vp, C.POINTER(DdpmTables), vp, vp, u64, u64, f32, f32, i32, vp, vp]
         d.ddif_plan_sample_ddim.argtypes = [vp, C.POINTER(DdimTables), vp, vp, u64, u64, f32, f32, i32, vp, vp]
         d.ddif_plan_sample_dpmpp.argtypes = [vp, C.POINTER(DpmTables), vp, f32, f32, i32, vp, vp]
+        d.ddif_plan_sample_dpm.argtypes = [vp, C.POINTER(DpmProgram), vp, f32, f32, i32, vp, vp, vp]
         d.ddif_plan_q_sample_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         d.ddif_plan_set_objective.argtypes = [vp, i32, i32]
         d.ddif_plan_get_objective.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
@@ -720,6 +735,43 @@ class PlanHandle:
             self.lib.check(self.lib.dll.ddif_plan_sample_dpmpp(self.h, C.byref(t), _ptr(x_T), lo, hi, do, _ptr(out),
                                                                _stream(self.lib, x_T.device)), "ddif_plan_sample_dpmpp")
             return out
+
+        return self._guarded(run, x_T.device)
+
+    @staticmethod
+    def dpm_program(ops, algorithm) -> "tuple[DpmProgram, C.Array]":
+        """include/ddif.h ddif_dpm_program from a list of op dicts: kind "eval" | "update" | "final" | "emit"; eval / final: t_model, alpha, sigma, src, dst;
+        update: form "multi" | "lin1" | "lin2" | "tay3", order, src, dst, m (3 model registers), c (up to 9 floats); emit: src.  Returns the struct and the
+        array it points into (keep it alive over the call)."""
+        if algorithm not in DPM_ALGORITHMS:
+            raise DdifError(f"algorithm {algorithm!r}: expected one of {sorted(DPM_ALGORITHMS)}")
+        arr = (DpmOp * max(1, len(ops)))()
+        for o, op in zip(arr, ops):
+            o.kind = DPM_OP_KINDS[op["kind"]]
+            o.src, o.dst = int(op.get("src", 0)), int(op.get("dst", 0))
+            if op["kind"] == "update":
+                o.form, o.order = DPM_FORMS[op["form"]], int(op.get("order", 0))
+                for j, r in enumerate(op["m"]):
+                    o.m[j] = int(r)
+                for j, v in enumerate(op["c"]):
+                    o.c[j] = float(v)
+            elif op["kind"] in ("eval", "final"):
+                o.t_model, o.alpha, o.sigma = float(op["t_model"]), float(op["alpha"]), float(op["sigma"])
+        return DpmProgram(len(ops), DPM_ALGORITHMS[algorithm], C.cast(arr, C.POINTER(DpmOp))), arr
+
+    def sample_dpm(self, ops, algorithm: str, x_T: torch.Tensor, clamp):
+        """One solver program (ddif_plan_sample_dpm) -> (out, inter): inter stacks one (B,C,H,W) image per "emit" op, or is None without any."""
+        self._check_sampler_inputs(x_T, None, 0)
+        x_T = x_T.contiguous()
+        prog, keep = self.dpm_program(ops, algorithm)
+        n_emit = sum(1 for op in ops if op["kind"] == "emit")
+        out = torch.empty_like(x_T)
+        inter = torch.empty((n_emit,) + tuple(x_T.shape), dtype=torch.float32, device=x_T.device) if n_emit else None
+        lo, hi, do = (clamp[0], clamp[1], 1) if clamp is not None else (0.0, 0.0, 0)
+        def run():
+            self.lib.check(self.lib.dll.ddif_plan_sample_dpm(self.h, C.byref(prog), _ptr(x_T), lo, hi, do, _ptr(out), _ptr(inter),
+                                                             _stream(self.lib, x_T.device)), "ddif_plan_sample_dpm")
+            return out, inter
 
         return self._guarded(run, x_T.device)
 

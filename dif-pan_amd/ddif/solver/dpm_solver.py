@@ -1,14 +1,18 @@
 """Drop-in for the part of the reference `solver/dpm_solver.py` (vendored DPM-Solver v2) that the DDIF hot path
-reaches: `NoiseScheduleVP('discrete')` (:6-175), `model_wrapper` (:178-342) and `DPM_Solver.sample(method="multistep")`
-(:345-459, 555-588, 804-912, 1055-1253).
+reaches: `NoiseScheduleVP('discrete')` (:6-175), `model_wrapper` (:178-342) and `DPM_Solver` (:345-962, 1020-1253) with
+`sample(method="multistep" | "singlestep" | "singlestep_fixed")`, both solver types and both algorithm types.
 
 Scalar schedule math stays on the host as fp32 torch scalars (the reference evaluates the same expressions as 0-d /
 1-element fp32 tensors); the tensor work of a whole sampling run -- every network evaluation, the x_start<->eps
 round trip, the corrector (the image-space clamp or dynamic thresholding, whose per-sample quantile is a selection
 kernel in front of the data prediction) and the multistep updates -- is ONE call into libddif (`ddif_plan_sample_dpmpp`)
-when the model is a ddif `UNetSR3`.  Any other model / corrector takes the generic loop below (same algorithm, model
-called per evaluation; dynamic thresholding there is the stateless `ddif_dynamic_threshold`).  Out of scope and rejected
-loudly: continuous schedules, singlestep / adaptive solvers, classifier guidance.
+when the model is a ddif `UNetSR3`.  Singlestep runs, solver_type="taylor", algorithm_type="dpmsolver", denoise_to_zero
+and return_intermediate are ONE call too (`ddif_plan_sample_dpm`) on a solver program built here: a flat op list over a few
+state and model registers, every scalar the reference's own fp32 expression (`_build_program`).  Any other model / corrector
+takes the generic loops below (same algorithm, model called per evaluation through the reference's update methods; dynamic
+thresholding there is the stateless `ddif_dynamic_threshold`).  Out of scope and rejected loudly: continuous schedules, the
+adaptive solver (its step size depends on a norm read back from the device every step), classifier guidance (SURVEY.md
+section 2, row 3).
 """
 from __future__ import annotations
 
@@ -174,27 +178,38 @@ class DPM_Solver:
         h = lam_t - lam_0
         a_t = torch.exp(ns.marginal_log_mean_coeff(t))
         s_t, s_0 = ns.marginal_std(t), ns.marginal_std(tprev[-1])
-        phi1 = torch.expm1(-h)
-        c = dict(cx=float(s_t / s_0), a_phi1=float(a_t * phi1), inv_r0=0.0, inv_r1=0.0, r0_frac=0.0, inv_r01=0.0,
-                 a_phi2=0.0, a_phi3=0.0)
+        pp = self.algorithm_type == "dpmsolver++"
+        phi1 = torch.expm1(-h) if pp else torch.expm1(h)
+        if pp:
+            c = dict(cx=float(s_t / s_0), a_phi1=float(a_t * phi1))
+        else:  # noise prediction (:590-596, 846-853, 902-911): the same update expressions over another coefficient family
+            c = dict(cx=float(torch.exp(ns.marginal_log_mean_coeff(t) - ns.marginal_log_mean_coeff(tprev[-1]))), a_phi1=float(s_t * phi1))
+        c.update(inv_r0=0.0, inv_r1=0.0, r0_frac=0.0, inv_r01=0.0, a_phi2=0.0, a_phi3=0.0)
         if order >= 2:
             h0 = lam_0 - ns.marginal_lambda(tprev[-2])
             r0 = h0 / h
             c["inv_r0"] = float(1.0 / r0)
+            # solver_type="taylor", order 2 (:841-845, 855-859): x_t = cx*x - a_phi1*m0 + tay2 * D1_0
+            c["tay2"] = float(a_t * (phi1 / h + 1.0)) if pp else -float(s_t * (phi1 / h - 1.0))
         if order == 3:
             h1 = ns.marginal_lambda(tprev[-2]) - ns.marginal_lambda(tprev[-3])
             r1 = h1 / h
-            phi2 = phi1 / h + 1.0
+            phi2 = phi1 / h + 1.0 if pp else phi1 / h - 1.0
             phi3 = phi2 / h - 0.5
-            c.update(inv_r1=float(1.0 / r1), r0_frac=float(r0 / (r0 + r1)), inv_r01=float(1.0 / (r0 + r1)),
-                     a_phi2=float(a_t * phi2), a_phi3=float(a_t * phi3))
+            c.update(inv_r1=float(1.0 / r1), r0_frac=float(r0 / (r0 + r1)), inv_r01=float(1.0 / (r0 + r1)))
+            if pp:
+                c.update(a_phi2=float(a_t * phi2), a_phi3=float(a_t * phi3))
+            else:  # - (sigma_t * phi_2) * D1: the minus goes into the scalar
+                c.update(a_phi2=-float(s_t * phi2), a_phi3=float(s_t * phi3))
         return c
 
     @staticmethod
-    def _apply_update(x, models, c, order):
+    def _apply_update(x, models, c, order, taylor=False):
         m0 = models[-1]
         v = c["cx"] * x - c["a_phi1"] * m0
-        if order == 2:
+        if order == 2 and taylor:
+            v = v + c["tay2"] * (c["inv_r0"] * (m0 - models[-2]))
+        elif order == 2:
             d1 = c["inv_r0"] * (m0 - models[-2])
             v = v - (0.5 * c["a_phi1"]) * d1
         elif order == 3:
@@ -209,7 +224,7 @@ class DPM_Solver:
         """(UNetSR3, cond, clamp) when the whole run can execute inside libddif, else None.  clamp: None, (lo, hi) of an ImageSpaceClamp, or the
         string "dynamic" for this solver's own dynamic_thresholding_fn (the plan's threshold mode "solver")."""
         meta = getattr(self._model_fn, "ddif", None)
-        if meta is None or self.algorithm_type != "dpmsolver++" or self.correcting_xt_fn is not None:
+        if meta is None or self.correcting_xt_fn is not None:  # (under algorithm_type="dpmsolver" the corrector reaches the library for the final denoise only)
             return None
         from ..models.sr3_dwt import UNetSR3
 
@@ -229,15 +244,302 @@ class DPM_Solver:
                 return meta["model"], cond, (cx0.lo, cx0.hi)
         return None
 
+    # ---- singlestep scalars (reference :555-600, 602-802), fp32 1-element tensors / Python floats exactly as the reference forms them ---------------
+    def _first_coefs(self, s, t):
+        """(c0, c1) of x_t = c0 * x - c1 * model_s (:577-600)."""
+        ns = self.noise_schedule
+        h = ns.marginal_lambda(t) - ns.marginal_lambda(s)
+        if self.algorithm_type == "dpmsolver++":
+            return float(ns.marginal_std(t) / ns.marginal_std(s)), float(torch.exp(ns.marginal_log_mean_coeff(t)) * torch.expm1(-h))
+        return float(torch.exp(ns.marginal_log_mean_coeff(t) - ns.marginal_log_mean_coeff(s))), float(ns.marginal_std(t) * torch.expm1(h))
+
+    def _second_coefs(self, s, t, r1, solver_type):
+        """s1 and the scalars of x_s1 = c0*x - c1*m_s and x_t = (c0*x - c1*m_s) + c2*(m_s1 - m_s) (:619-677)."""
+        if solver_type not in ["dpmsolver", "taylor"]:
+            raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
+        if r1 is None:
+            r1 = 0.5
+        ns = self.noise_schedule
+        lambda_s, lambda_t = ns.marginal_lambda(s), ns.marginal_lambda(t)
+        h = lambda_t - lambda_s
+        s1 = ns.inverse_lambda(lambda_s + r1 * h)
+        log_alpha_s, log_alpha_s1, log_alpha_t = ns.marginal_log_mean_coeff(s), ns.marginal_log_mean_coeff(s1), ns.marginal_log_mean_coeff(t)
+        sigma_s, sigma_s1, sigma_t = ns.marginal_std(s), ns.marginal_std(s1), ns.marginal_std(t)
+        alpha_s1, alpha_t = torch.exp(log_alpha_s1), torch.exp(log_alpha_t)
+        if self.algorithm_type == "dpmsolver++":
+            phi_11, phi_1 = torch.expm1(-r1 * h), torch.expm1(-h)
+            xs1 = (sigma_s1 / sigma_s, alpha_s1 * phi_11)
+            c2 = -((0.5 / r1) * (alpha_t * phi_1)) if solver_type == "dpmsolver" else (1. / r1) * (alpha_t * (phi_1 / h + 1.))
+            xt = (sigma_t / sigma_s, alpha_t * phi_1, c2)
+        else:
+            phi_11, phi_1 = torch.expm1(r1 * h), torch.expm1(h)
+            xs1 = (torch.exp(log_alpha_s1 - log_alpha_s), sigma_s1 * phi_11)
+            c2 = -((0.5 / r1) * (sigma_t * phi_1)) if solver_type == "dpmsolver" else -((1. / r1) * (sigma_t * (phi_1 / h - 1.)))
+            xt = (torch.exp(log_alpha_t - log_alpha_s), sigma_t * phi_1, c2)
+        return dict(s1=s1, xs1=tuple(float(v) for v in xs1), xt=tuple(float(v) for v in xt))
+
+    def _third_coefs(self, s, t, r1, r2, solver_type):
+        """s1, s2 and the scalars of x_s1, x_s2 and x_t (:703-797).  xt: 3 scalars (lin2 over m_s2 - m_s) or the 9 of tay3 (csrc/kernels_misc.h)."""
+        if solver_type not in ["dpmsolver", "taylor"]:
+            raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
+        if r1 is None:
+            r1 = 1. / 3.
+        if r2 is None:
+            r2 = 2. / 3.
+        ns = self.noise_schedule
+        lambda_s, lambda_t = ns.marginal_lambda(s), ns.marginal_lambda(t)
+        h = lambda_t - lambda_s
+        s1 = ns.inverse_lambda(lambda_s + r1 * h)
+        s2 = ns.inverse_lambda(lambda_s + r2 * h)
+        log_alpha_s, log_alpha_s1, log_alpha_s2, log_alpha_t = (ns.marginal_log_mean_coeff(s), ns.marginal_log_mean_coeff(s1), ns.marginal_log_mean_coeff(s2),
+                                                                ns.marginal_log_mean_coeff(t))
+        sigma_s, sigma_s1, sigma_s2, sigma_t = ns.marginal_std(s), ns.marginal_std(s1), ns.marginal_std(s2), ns.marginal_std(t)
+        alpha_s1, alpha_s2, alpha_t = torch.exp(log_alpha_s1), torch.exp(log_alpha_s2), torch.exp(log_alpha_t)
+        if self.algorithm_type == "dpmsolver++":
+            phi_11, phi_12, phi_1 = torch.expm1(-r1 * h), torch.expm1(-r2 * h), torch.expm1(-h)
+            phi_22 = torch.expm1(-r2 * h) / (r2 * h) + 1.
+            phi_2 = phi_1 / h + 1.
+            phi_3 = phi_2 / h - 0.5
+            xs1 = (sigma_s1 / sigma_s, alpha_s1 * phi_11)
+            xs2 = (sigma_s2 / sigma_s, alpha_s2 * phi_12, r2 / r1 * (alpha_s2 * phi_22))
+            base = (sigma_t / sigma_s, alpha_t * phi_1)
+            if solver_type == "dpmsolver":
+                xt = base + ((1. / r2) * (alpha_t * phi_2),)
+            else:
+                xt = base + (alpha_t * phi_2, 1. / r1, 1. / r2, r1, r2, r2 - r1, alpha_t * phi_3)
+        else:
+            phi_11, phi_12, phi_1 = torch.expm1(r1 * h), torch.expm1(r2 * h), torch.expm1(h)
+            phi_22 = torch.expm1(r2 * h) / (r2 * h) - 1.
+            phi_2 = phi_1 / h - 1.
+            phi_3 = phi_2 / h - 0.5
+            xs1 = (torch.exp(log_alpha_s1 - log_alpha_s), sigma_s1 * phi_11)
+            xs2 = (torch.exp(log_alpha_s2 - log_alpha_s), sigma_s2 * phi_12, -(r2 / r1 * (sigma_s2 * phi_22)))
+            base = (torch.exp(log_alpha_t - log_alpha_s), sigma_t * phi_1)
+            if solver_type == "dpmsolver":
+                xt = base + (-((1. / r2) * (sigma_t * phi_2)),)
+            else:
+                xt = base + (-(sigma_t * phi_2), 1. / r1, 1. / r2, r1, r2, r2 - r1, sigma_t * phi_3)
+        f = lambda tup: tuple(float(v) for v in tup)
+        return dict(s1=s1, s2=s2, xs1=f(xs1), xs2=f(xs2), xt=f(xt))
+
+    @staticmethod
+    def _lin2(x, m0, c, ma=None, mb=None):
+        v = c[0] * x - c[1] * m0
+        return v if ma is None else v + c[2] * (ma - mb)
+
+    @staticmethod
+    def _tay3(x, m0, m1, m2, c):
+        """c = (c0, c1, a_phi2, 1/r1, 1/r2, r1, r2, r2 - r1, a_phi3) (:749-758, 788-797)."""
+        D1_0 = c[3] * (m1 - m0)
+        D1_1 = c[4] * (m2 - m0)
+        D1 = (c[6] * D1_0 - c[5] * D1_1) / c[7]
+        D2 = 2. * (D1_1 - D1_0) / c[7]
+        return ((c[0] * x - c[1] * m0) + c[2] * D1) - c[8] * D2
+
+    # ---- the reference's update methods (signatures and defaults of :490-1053); they carry the generic path --------------------------------------
+    def get_orders_and_timesteps_for_singlestep_solver(self, steps, order, skip_type, t_T, t_0, device=None):
+        if order == 3:
+            K = steps // 3 + 1
+            if steps % 3 == 0:
+                orders = [3, ] * (K - 2) + [2, 1]
+            elif steps % 3 == 1:
+                orders = [3, ] * (K - 1) + [1]
+            else:
+                orders = [3, ] * (K - 1) + [2]
+        elif order == 2:
+            if steps % 2 == 0:
+                K = steps // 2
+                orders = [2, ] * K
+            else:
+                K = steps // 2 + 1
+                orders = [2, ] * (K - 1) + [1]
+        elif order == 1:
+            K = 1
+            orders = [1, ] * steps
+        else:
+            raise ValueError("'order' must be '1' or '2' or '3'.")
+        if skip_type == "logSNR":
+            timesteps_outer = self.get_time_steps(skip_type, t_T, t_0, K, device)  # (order 1: K = 1 -- two times for `steps` updates, as in the reference)
+        else:
+            timesteps_outer = self.get_time_steps(skip_type, t_T, t_0, steps, device)[torch.cumsum(torch.tensor([0, ] + orders), 0)]
+        return timesteps_outer, orders
+
+    def denoise_to_zero_fn(self, x, s):
+        return self.data_prediction_fn(x, s)
+
+    def dpm_solver_first_update(self, x, s, t, model_s=None, return_intermediate=False):
+        c = self._first_coefs(s, t)
+        if model_s is None:
+            model_s = self.model_fn(x, s)
+        x_t = self._lin2(x, model_s, c)
+        return (x_t, {"model_s": model_s}) if return_intermediate else x_t
+
+    def singlestep_dpm_solver_second_update(self, x, s, t, r1=0.5, model_s=None, return_intermediate=False, solver_type="dpmsolver"):
+        c = self._second_coefs(s, t, r1, solver_type)
+        if model_s is None:
+            model_s = self.model_fn(x, s)
+        x_s1 = self._lin2(x, model_s, c["xs1"])
+        model_s1 = self.model_fn(x_s1, c["s1"])
+        x_t = self._lin2(x, model_s, c["xt"], model_s1, model_s)
+        return (x_t, {"model_s": model_s, "model_s1": model_s1}) if return_intermediate else x_t
+
+    def singlestep_dpm_solver_third_update(self, x, s, t, r1=1. / 3., r2=2. / 3., model_s=None, model_s1=None, return_intermediate=False, solver_type="dpmsolver"):
+        c = self._third_coefs(s, t, r1, r2, solver_type)
+        if model_s is None:
+            model_s = self.model_fn(x, s)
+        if model_s1 is None:
+            x_s1 = self._lin2(x, model_s, c["xs1"])
+            model_s1 = self.model_fn(x_s1, c["s1"])
+        x_s2 = self._lin2(x, model_s, c["xs2"], model_s1, model_s)
+        model_s2 = self.model_fn(x_s2, c["s2"])
+        if solver_type == "dpmsolver":
+            x_t = self._lin2(x, model_s, c["xt"], model_s2, model_s)
+        else:
+            x_t = self._tay3(x, model_s, model_s1, model_s2, c["xt"])
+        return (x_t, {"model_s": model_s, "model_s1": model_s1, "model_s2": model_s2}) if return_intermediate else x_t
+
+    def multistep_dpm_solver_second_update(self, x, model_prev_list, t_prev_list, t, solver_type="dpmsolver"):
+        if solver_type not in ["dpmsolver", "taylor"]:
+            raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
+        c = self._update_coefs([tp.reshape(1) for tp in t_prev_list[-2:]], t.reshape(1), 2)
+        return self._apply_update(x, list(model_prev_list[-2:]), c, 2, taylor=solver_type == "taylor")
+
+    def multistep_dpm_solver_third_update(self, x, model_prev_list, t_prev_list, t, solver_type="dpmsolver"):
+        model_prev_2, model_prev_1, model_prev_0 = model_prev_list
+        t_prev_2, t_prev_1, t_prev_0 = t_prev_list
+        c = self._update_coefs([t_prev_2.reshape(1), t_prev_1.reshape(1), t_prev_0.reshape(1)], t.reshape(1), 3)
+        return self._apply_update(x, [model_prev_2, model_prev_1, model_prev_0], c, 3)
+
+    def singlestep_dpm_solver_update(self, x, s, t, order, return_intermediate=False, solver_type="dpmsolver", r1=None, r2=None):
+        if order == 1:
+            return self.dpm_solver_first_update(x, s, t, return_intermediate=return_intermediate)
+        elif order == 2:
+            return self.singlestep_dpm_solver_second_update(x, s, t, return_intermediate=return_intermediate, solver_type=solver_type, r1=r1)
+        elif order == 3:
+            return self.singlestep_dpm_solver_third_update(x, s, t, return_intermediate=return_intermediate, solver_type=solver_type, r1=r1, r2=r2)
+        raise ValueError("Solver order must be 1 or 2 or 3, got {}".format(order))
+
+    def multistep_dpm_solver_update(self, x, model_prev_list, t_prev_list, t, order, solver_type="dpmsolver"):
+        if order == 1:
+            return self.dpm_solver_first_update(x, t_prev_list[-1], t, model_s=model_prev_list[-1])
+        elif order == 2:
+            return self.multistep_dpm_solver_second_update(x, model_prev_list, t_prev_list, t, solver_type=solver_type)
+        elif order == 3:
+            return self.multistep_dpm_solver_third_update(x, model_prev_list, t_prev_list, t, solver_type=solver_type)
+        raise ValueError("Solver order must be 1 or 2 or 3, got {}".format(order))
+
+    def add_noise(self, x, t, noise=None):
+        """x_t = alpha_t * x + sigma_t * noise for every time of t: (t_size, batch_size, *shape), squeezed for one time (:1020-1038)."""
+        alpha_t, sigma_t = self.noise_schedule.marginal_alpha(t).to(x.device), self.noise_schedule.marginal_std(t).to(x.device)
+        if noise is None:
+            noise = torch.randn((t.shape[0], *x.shape), device=x.device)
+        x = x.reshape((-1, *x.shape))
+        shape = (-1,) + (1,) * (x.dim() - 1)
+        xt = alpha_t.reshape(shape) * x + sigma_t.reshape(shape) * noise
+        return xt.squeeze(0) if t.shape[0] == 1 else xt
+
+    def inverse(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type="time_uniform", method="multistep", lower_order_final=True,
+                denoise_to_zero=False, solver_type="dpmsolver", atol=0.0078, rtol=0.05, return_intermediate=False):
+        t_0 = 1. / self.noise_schedule.total_N if t_start is None else t_start
+        t_T = self.noise_schedule.T if t_end is None else t_end
+        assert t_0 > 0 and t_T > 0, "Time range needs to be greater than 0. For discrete-time DPMs, it needs to be in [1 / N, 1], where N is the length of betas array"
+        return self.sample(x, steps=steps, t_start=t_0, t_end=t_T, order=order, skip_type=skip_type, method=method, lower_order_final=lower_order_final,
+                           denoise_to_zero=denoise_to_zero, solver_type=solver_type, atol=atol, rtol=rtol, return_intermediate=return_intermediate)
+
+    # ---- the schedule of a run: shared by the generic loop and the solver program -------------------------------------------------------------------
+    @staticmethod
+    def _multistep_orders(steps, order, lower_order_final):
+        """Order of the update INTO timesteps[step], step = 1 .. steps (:1193-1210); lower_order_final only with steps < 10."""
+        return [step if step < order else (min(order, steps + 1 - step) if lower_order_final and steps < 10 else order) for step in range(1, steps + 1)]
+
+    def _singlestep_schedule(self, steps, order, skip_type, method, t_T, t_0):
+        """[(s, t, order, r1, r2)] per outer step (:1223-1235); s, t 0-d fp32 tensors, r1 / r2 0-d fp32 tensors or None."""
+        if method == "singlestep":
+            timesteps_outer, orders = self.get_orders_and_timesteps_for_singlestep_solver(steps=steps, order=order, skip_type=skip_type, t_T=t_T, t_0=t_0)
+        else:
+            K = steps // order
+            orders = [order, ] * K
+            timesteps_outer = self.get_time_steps(skip_type, t_T, t_0, K)
+        sched = []
+        for step, o in enumerate(orders):
+            s, t = timesteps_outer[step], timesteps_outer[step + 1]  # (singlestep, order 1, logSNR: IndexError at step 1, as in the reference)
+            timesteps_inner = self.get_time_steps(skip_type, s.item(), t.item(), o)
+            lambda_inner = self.noise_schedule.marginal_lambda(timesteps_inner)
+            h = lambda_inner[-1] - lambda_inner[0]
+            r1 = None if o <= 1 else (lambda_inner[1] - lambda_inner[0]) / h
+            r2 = None if o <= 2 else (lambda_inner[2] - lambda_inner[0]) / h
+            sched.append((s, t, o, r1, r2))
+        return sched
+
+    def _eval_op(self, t, src, dst, kind="eval"):
+        ns = self.noise_schedule
+        t1 = t.reshape(1)
+        return dict(kind=kind, t=t1, t_model=float((t1 - 1.0 / ns.total_N) * 1000.0), alpha=float(ns.marginal_alpha(t1)), sigma=float(ns.marginal_std(t1)), src=src, dst=dst)
+
+    def _build_program(self, steps, order, skip_type, method, lower_order_final, denoise_to_zero, solver_type, return_intermediate, t_T, t_0):
+        """The run as a flat op list over state registers (0 x, 1 x_s1, 2 x_s2) and model registers (include/ddif.h ddif_dpm_program).  Every scalar is the
+        reference's own fp32 torch expression; `t` of an evaluation (its continuous time, a 1-element fp32 tensor) stays on the op for the tests."""
+        ops = []
+        emit = (lambda: ops.append(dict(kind="emit", src=0))) if return_intermediate else (lambda: None)
+        pad = lambda c: list(c) + [0.0] * (9 - len(c))
+        if method == "multistep":
+            assert steps >= order
+            ts = self.get_time_steps(skip_type, t_T, t_0, steps)
+            assert ts.shape[0] - 1 == steps
+            ords = self._multistep_orders(steps, order, lower_order_final)
+            ops.append(self._eval_op(ts[0], 0, 0))
+            emit()  # the initial x (:1190-1191)
+            for step in range(1, steps + 1):
+                o = ords[step - 1]
+                c = self._update_coefs([ts[j].reshape(1) for j in range(step - o, step)], ts[step].reshape(1), o)
+                m = [(step - 1 - j) % 3 for j in range(3)]  # newest first
+                if o == 2 and solver_type == "taylor":
+                    ops.append(dict(kind="update", form="lin2", order=0, src=0, dst=0, m=[m[0], m[0], m[1]], c=pad([c["cx"], c["a_phi1"], c["tay2"], c["inv_r0"]])))
+                else:
+                    ops.append(dict(kind="update", form="multi", order=o, src=0, dst=0, m=m,
+                                    c=pad([c["cx"], c["a_phi1"], c["inv_r0"], c["inv_r1"], c["r0_frac"], c["inv_r01"], c["a_phi2"], c["a_phi3"]])))
+                emit()
+                if step < steps:  # the final model value is never needed (:1219-1221)
+                    ops.append(self._eval_op(ts[step], 0, step % 3))
+        else:
+            for s, t, o, r1, r2 in self._singlestep_schedule(steps, order, skip_type, method, t_T, t_0):
+                ops.append(self._eval_op(s, 0, 0))
+                if o == 1:
+                    ops.append(dict(kind="update", form="lin1", order=0, src=0, dst=0, m=[0, 0, 0], c=pad(self._first_coefs(s, t))))
+                elif o == 2:
+                    c = self._second_coefs(s, t, r1, solver_type)
+                    ops.append(dict(kind="update", form="lin1", order=0, src=0, dst=1, m=[0, 0, 0], c=pad(c["xs1"])))
+                    ops.append(self._eval_op(c["s1"], 1, 1))
+                    ops.append(dict(kind="update", form="lin2", order=0, src=0, dst=0, m=[0, 1, 0], c=pad(list(c["xt"]) + [1.0])))
+                else:
+                    c = self._third_coefs(s, t, r1, r2, solver_type)
+                    ops.append(dict(kind="update", form="lin1", order=0, src=0, dst=1, m=[0, 0, 0], c=pad(c["xs1"])))
+                    ops.append(self._eval_op(c["s1"], 1, 1))
+                    ops.append(dict(kind="update", form="lin2", order=0, src=0, dst=2, m=[0, 1, 0], c=pad(list(c["xs2"]) + [1.0])))
+                    ops.append(self._eval_op(c["s2"], 2, 2))
+                    if solver_type == "dpmsolver":
+                        ops.append(dict(kind="update", form="lin2", order=0, src=0, dst=0, m=[0, 2, 0], c=pad(list(c["xt"]) + [1.0])))
+                    else:
+                        ops.append(dict(kind="update", form="tay3", order=0, src=0, dst=0, m=[0, 1, 2], c=pad(c["xt"])))
+                emit()
+        if denoise_to_zero:
+            ops.append(self._eval_op(torch.ones((1,)) * t_0, 0, 0, kind="final"))
+            emit()
+        return ops
+
     def sample(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type="time_uniform", method="multistep",
                lower_order_final=True, denoise_to_zero=False, solver_type="dpmsolver", atol=0.0078, rtol=0.05,
                return_intermediate=False):
-        if method != "multistep":
-            raise DdifError(f"DPM_Solver.sample(method='{method}'): only 'multistep' is in scope of the HIP path")
-        if solver_type != "dpmsolver":
-            raise DdifError("solver_type='taylor' is out of scope of the HIP path")
-        if self.algorithm_type != "dpmsolver++":
-            raise DdifError("algorithm_type='dpmsolver' (noise prediction updates) is out of scope of the HIP path")
+        if method == "adaptive":
+            raise DdifError("DPM_Solver.sample(method='adaptive'): the adaptive solver sizes every step from a norm of the iterate that would have to be read back "
+                            "from the device each step; out of scope of the HIP path (use 'singlestep', 'singlestep_fixed' or 'multistep')")
+        if method not in ("multistep", "singlestep", "singlestep_fixed"):
+            raise ValueError("Got wrong method {}".format(method))
+        if solver_type not in ("dpmsolver", "taylor"):
+            raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
+        plain = method == "multistep" and solver_type == "dpmsolver" and self.algorithm_type == "dpmsolver++" and not denoise_to_zero and not return_intermediate
+        if not plain:
+            return self._sample_program(x, steps, t_start, t_end, order, skip_type, method, lower_order_final, denoise_to_zero, solver_type, return_intermediate)
         ns = self.noise_schedule
         t_0 = 1.0 / ns.total_N if t_end is None else t_end
         t_T = ns.T if t_start is None else t_start
@@ -278,7 +580,6 @@ class DPM_Solver:
             with torch.no_grad():
                 return plan.sample_dpmpp(tabs, x, clamp)
         # generic loop: same algorithm, the model is called once per evaluation (reference :1179-1221)
-        inter = []
         with torch.no_grad():
             models: List[torch.Tensor] = []
             for k in range(steps):
@@ -286,8 +587,70 @@ class DPM_Solver:
                 x = self._apply_update(x, models, coefs[k], ords[k])
                 if self.correcting_xt_fn is not None:
                     x = self.correcting_xt_fn(x, ts[k + 1].reshape(1), k + 1)
-                inter.append(x)
+        return x
+
+    def _sample_program(self, x, steps, t_start, t_end, order, skip_type, method, lower_order_final, denoise_to_zero, solver_type, return_intermediate):
+        """Everything beyond the plain multistep DPM-Solver++ run: singlestep / singlestep_fixed, solver_type="taylor", algorithm_type="dpmsolver", the final
+        denoise, intermediates.  One library call (ddif_plan_sample_dpm) on a solver program when the run can be fused, else the reference's loop (:1179-1249)
+        over the update methods above."""
+        ns = self.noise_schedule
+        t_0 = 1.0 / ns.total_N if t_end is None else t_end
+        t_T = ns.T if t_start is None else t_start
+        assert t_0 > 0 and t_T > 0, "Time range needs to be greater than 0. For discrete-time DPMs, it needs to be in [1 / N, 1], where N is the length of betas array"
+        fused = self._fused_target()
+        if fused is not None:
+            ops = self._build_program(steps, order, skip_type, method, lower_order_final, denoise_to_zero, solver_type, return_intermediate, t_T, t_0)
+            model, cond, clamp = fused
+            B, _, H, W = x.shape
+            plan = model.plan_for(B, H, W, x.device)
+            plan.set_objective(self._model_fn.ddif["model_type"], plan.objective[1])
+            if clamp == "dynamic":
+                plan.set_threshold("solver", float(self.dynamic_thresholding_ratio), float(self.thresholding_max_val))
+                clamp = None
+            else:
+                plan.set_threshold("off")
+            plan.set_cond(cond)
+            with torch.no_grad():
+                out, inter = plan.sample_dpm(ops, self.algorithm_type, x, clamp)
+            return (out, list(inter.unbind(0))) if return_intermediate else out
+        intermediates = []
+        with torch.no_grad():
+            if method == "multistep":
+                assert steps >= order
+                timesteps = self.get_time_steps(skip_type, t_T, t_0, steps)
+                assert timesteps.shape[0] - 1 == steps
+                ords = self._multistep_orders(steps, order, lower_order_final)
+                step = 0
+                t = timesteps[step]
+                t_prev_list = [t]
+                model_prev_list = [self.model_fn(x, t)]
+                if self.correcting_xt_fn is not None:
+                    x = self.correcting_xt_fn(x, t, step)
+                if return_intermediate:
+                    intermediates.append(x)
+                for step in range(1, steps + 1):
+                    t = timesteps[step]
+                    o = ords[step - 1]
+                    x = self.multistep_dpm_solver_update(x, model_prev_list, t_prev_list, t, o, solver_type=solver_type)
+                    if self.correcting_xt_fn is not None:
+                        x = self.correcting_xt_fn(x, t, step)
+                    if return_intermediate:
+                        intermediates.append(x)
+                    if step < steps:  # the final model value is never needed (:1219-1221)
+                        t_prev_list = (t_prev_list + [t])[-3:]
+                        model_prev_list = (model_prev_list + [self.model_fn(x, t)])[-3:]
+            else:
+                for step, (s, t, o, r1, r2) in enumerate(self._singlestep_schedule(steps, order, skip_type, method, t_T, t_0)):
+                    x = self.singlestep_dpm_solver_update(x, s, t, o, solver_type=solver_type, r1=r1, r2=r2)
+                    if self.correcting_xt_fn is not None:
+                        x = self.correcting_xt_fn(x, t, step)
+                    if return_intermediate:
+                        intermediates.append(x)
             if denoise_to_zero:
-                x = self.data_prediction_fn(x, torch.ones((1,)) * t_0)
-                inter.append(x)
-        return (x, inter) if return_intermediate else x
+                t = torch.ones((1,)) * t_0
+                x = self.denoise_to_zero_fn(x, t)
+                if self.correcting_xt_fn is not None:
+                    x = self.correcting_xt_fn(x, t, step + 1)
+                if return_intermediate:
+                    intermediates.append(x)
+        return (x, intermediates) if return_intermediate else x

@@ -151,6 +151,54 @@ typedef struct ddif_dpm_tables {
 DDIF_API int ddif_plan_sample_dpmpp(ddif_plan_t plan, const ddif_dpm_tables* tabs, const float* x_T, float clamp_lo,
                            float clamp_hi, int do_clamp, float* out, void* stream);
 
+/* DPM_Solver.sample as a host-built SOLVER PROGRAM (solver/dpm_solver.py:1055-1253): singlestep and singlestep_fixed runs (:602-802, 1222-1240), both
+ * algorithm types, both solver types, the final denoise (:549-553, 1243-1245) and the intermediates (:1190-1191, 1239-1240, 1248-1249).  The program is a flat
+ * list of ops over DDIF_DPM_NUM_REGS state registers (iterates; register 0 holds x_T at the start) and DDIF_DPM_NUM_REGS model registers (model values):
+ *   DDIF_DPM_EVAL           model[dst] = model value of net(state[src], t_model, cond).  Under DDIF_DPM_ALGO_DPMSOLVERPP that is the data prediction of
+ *                           ddif_plan_sample_dpmpp (model_type branch, x0 = (x - sigma * eps) / alpha, then the image-space clamp or dynamic thresholding);
+ *                           under DDIF_DPM_ALGO_DPMSOLVER the noise prediction alone (:435-439; the reference corrects inside data_prediction_fn only).
+ *   DDIF_DPM_UPDATE         state[dst] = form(state[src], model[m[0..2]], c[]); dst == src is fine.  Forms, each in the reference's operation order with a
+ *                           leading minus folded into its scalar:
+ *                             DDIF_DPM_FORM_MULTI  the multistep update of ddif_plan_sample_dpmpp, order 1..3: c = cx, a1, inv_r0, inv_r1, r0_frac, inv_r01, a2, a3
+ *                                                  (noise prediction :846-853, 902-911: cx = exp(log_alpha_t - log_alpha_prev), a1 = sigma_t * phi_1, a2 = -sigma_t * phi_2,
+ *                                                  a3 = sigma_t * phi_3); m[0] newest
+ *                             DDIF_DPM_FORM_LIN1   c0 * x - c1 * m0
+ *                             DDIF_DPM_FORM_LIN2   (c0 * x - c1 * m0) + c2 * (c3 * (m1 - m2))      m = {m0, m1, m2}; c3 = 1 wherever the reference has no second factor
+ *                             DDIF_DPM_FORM_TAY3   D1_0 = c3 * (m1 - m0), D1_1 = c4 * (m2 - m0), D1 = (c6 * D1_0 - c5 * D1_1) / c7, D2 = 2 * (D1_1 - D1_0) / c7,
+ *                                                  ((c0 * x - c1 * m0) + c2 * D1) - c8 * D2          c3 = 1 / r1, c4 = 1 / r2, c5 = r1, c6 = r2, c7 = r2 - r1
+ *   DDIF_DPM_FINAL_DENOISE  state[dst] = the data prediction WITH the corrector at state[src], under either algorithm (:549-553)
+ *   DDIF_DPM_EMIT           the next (B,C,H,W) slice of inter_out = state[src]
+ * One launch per evaluation behind the network (model value, corrector, store, and the update that follows it in the program); dynamic thresholding keeps its
+ * selection launch in front.  The program is validated before anything is enqueued: registers in range and written before they are read, orders 1..3, EMIT only
+ * with inter_out, do_clamp not together with DDIF_THRESHOLD_SOLVER -- DDIF_ERR_INVALID otherwise.  The sticky objective and threshold of the plan apply as in
+ * ddif_plan_sample_dpmpp.  out = state[0] after the last op. */
+#define DDIF_DPM_NUM_REGS 3
+#define DDIF_DPM_ALGO_DPMSOLVERPP 0
+#define DDIF_DPM_ALGO_DPMSOLVER 1
+#define DDIF_DPM_EVAL 0
+#define DDIF_DPM_UPDATE 1
+#define DDIF_DPM_FINAL_DENOISE 2
+#define DDIF_DPM_EMIT 3
+#define DDIF_DPM_FORM_MULTI 1
+#define DDIF_DPM_FORM_LIN2 2
+#define DDIF_DPM_FORM_TAY3 3
+#define DDIF_DPM_FORM_LIN1 4
+typedef struct ddif_dpm_op {
+    int32_t kind;                  /* DDIF_DPM_EVAL .. DDIF_DPM_EMIT */
+    int32_t form, order;           /* UPDATE: DDIF_DPM_FORM_*; order of FORM_MULTI */
+    int32_t src, dst;              /* registers, see above */
+    int32_t m[3];                  /* UPDATE: model registers (unused ones: any value in range) */
+    float t_model, alpha, sigma;   /* EVAL / FINAL_DENOISE: (t - 1/N) * 1000 and the marginal alpha / std at t */
+    float c[9];                    /* UPDATE */
+} ddif_dpm_op;
+typedef struct ddif_dpm_program {
+    int32_t n_ops;
+    int32_t algorithm;             /* DDIF_DPM_ALGO_* */
+    const ddif_dpm_op* ops;        /* HOST array */
+} ddif_dpm_program;
+DDIF_API int ddif_plan_sample_dpm(ddif_plan_t plan, const ddif_dpm_program* prog, const float* x_T, float clamp_lo, float clamp_hi, int do_clamp, float* out,
+                                  float* inter_out /* nullable: [number of EMIT ops][B][C][H][W] */, void* stream);
+
 /* GaussianDiffusion.p_losses forward half (diffusion/diffusion_ddpm_pan.py:692-732), eval mode, pred_mode x_start:
  * x_t = a[b]*x0 + s[b]*noise; pred = net(x_t, t, cond, self_cond); returns pred (recon_x0). a, s, time: B floats each, HOST or DEVICE
  * memory (copied on `stream`: a training loop that draws t on the device hands them over without a host round trip). */

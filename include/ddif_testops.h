@@ -109,6 +109,14 @@ DDIF_API int ddif_q_sample(const float* x0, const float* noise, const float* a, 
 /* F.l1_loss(pred, target), mean reduction: out = one device float */
 DDIF_API int ddif_l1_loss_fwd(const float* pred, const float* target, int64_t n, float* out, void* stream);
 
+/* ---- one launch of the solver programs' evaluation kernel (csrc/kernels_misc.h dpm_eval_update_kernel; include/ddif.h ddif_plan_sample_dpm) on plain arrays ----
+ * All device arrays hold n floats (thr: n / per floats, nullable; lms: needed with do_clamp).  net != NULL: the model value of (net, xe) under `algorithm`
+ * (DDIF_DPM_ALGO_*) and model_type 0 x_start / 1 noise / 2 v goes to m_out (nullable); form 0: out (nullable) = that model value.  form = DDIF_DPM_FORM_*: out =
+ * form(x, m0, m1, m2, c_host[9]) where a NULL m names the model value of this launch; net == NULL runs the update alone. */
+DDIF_API int ddif_dpm_eval_update(const float* net, const float* xe, const float* lms, const float* thr, int64_t n, int64_t per, float alpha, float sigma, float lo, float hi,
+                                  int do_clamp, int model_type, int algorithm, int form, int order, const float* x, const float* m0, const float* m1, const float* m2,
+                                  const float* c_host, float* m_out, float* out, void* stream);
+
 /* ---- the order statistics behind ddif_dynamic_threshold (csrc/kernels_quantile.h) ------------------------------------------
  * x device [B][n]; s_out device [B] = the interpolated quantile of |x_b| (max_val = 0); stats device [B][2] = the two order statistics of |x_b| it
  * interpolates between, rank floor(r) and ceil(r) of r = fp32(ratio) * fp32(n - 1): what torch.sort(|x_b|) holds at those indices, bit for bit. */

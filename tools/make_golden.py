@@ -12,6 +12,9 @@ written into the repository.
                                                                     fp32 + fp64 as above, plus the reference's quantile per (step, sample); not part of the default set)
     python tools/make_golden.py --only l1ssim                      (loss_type="l1ssim": the HybridL1SSIM operator, p_losses and its backward pass:
                                                                     tests/golden_cases_l1ssim.py; fp32 + fp64 as above; not part of the default set)
+    python tools/make_golden.py --only dpmx                        (DPM-Solver singlestep / singlestep_fixed, solver_type="taylor", algorithm_type="dpmsolver",
+                                                                    denoise_to_zero, return_intermediate: tests/golden_cases_dpmx.py; fp32 + fp64 as above,
+                                                                    plus orders, outer time steps and the time of every evaluation; not part of the default set)
 """
 import argparse
 import json
@@ -365,6 +368,94 @@ def make_dynthresh(UNetSR3, D, S, net_for):
         finish(cid, run, float(kw["thresholding_max_val"]), True, lambda out: 1e-4 * max(1.0, float(out.abs().max())), cond)
     assert not too_noisy, f"the reference's own fp32-fp64 gap exceeds a tenth of the tolerance: change these cases: {too_noisy}"
     assert not idle, f"thresholding is active in less than half of the (step, sample) pairs: change these cases: {idle}"
+
+
+def make_dpmx(UNetSR3, D, S, net_for):
+    """DPM-Solver beyond the plain multistep DPM-Solver++ run (tests/golden_cases_dpmx.py).  As make_dynthresh: the reference as it is (fp32: the expected
+    output) and its fp64 twin, schedule scalars in the solver's own fp32 in both.  From the fp32 run, by wrapping instance attributes of the solver: `eval_t`
+    (the time handed to `slv.model` at every evaluation, in execution order), `orders` (the order argument of every singlestep / multistep update call) and
+    `timesteps_outer` (what get_orders_and_timesteps_for_singlestep_solver returned, else the first get_time_steps grid)."""
+    import copy
+
+    import golden_cases_dpmx as gx
+
+    nets64 = {}
+
+    def net64_for(ds):
+        if ds not in nets64:
+            n = copy.deepcopy(net_for(ds)).double()
+            fwd = n.forward
+            n.forward = lambda x, t, cond=None, self_cond=None: fwd(x.double(), t, None if cond is None else cond.double(), None if self_cond is None else self_cond.double())
+            n.noise_level_mlp[0].register_forward_hook(lambda m, i, o: o.double())
+            nets64[ds] = n
+        return nets64[ds]
+
+    too_noisy = []
+    for case in gx.CASES:
+        cid, ds, H, T, seed, mt = case["cid"], case["ds"], case["H"], case["T"], case["seed"], case["model_type"]
+        C = gc.DATASETS[ds][0]
+        cond = gc.tiles_for(ds, 1, H, H, seed=seed)["cond"]
+        xT = torch.randn(1, C, H, H, generator=torch.Generator().manual_seed(seed))
+        betas = D.make_beta_schedule(**gx.schedule_kwargs(case["schedule"], T))
+        betas = torch.as_tensor(betas).float()
+
+        def run(f64, rec, inter=False):
+            net = net64_for(ds) if f64 else net_for(ds)
+            cnd, x = (cond.double(), xT.double()) if f64 else (cond, xT)
+            ns = S.NoiseScheduleVP("discrete", betas=betas)
+            fn = S.model_wrapper(net, ns, model_type=mt, guidance_type="classifier-free", guidance_scale=1.0, condition=cnd)
+            lms = cnd[:, :C]
+            corr = {"clamp": lambda x0, t: (x0 + lms).clamp(0, 1.0) - lms, "dyn": "dynamic_thresholding", None: None}[case["corrector"]]
+            slv = S.DPM_Solver(fn, ns, algorithm_type=case["algorithm"], correcting_x0_fn=corr)
+            if rec is not None:
+                model, gts, gos = slv.model, slv.get_time_steps, slv.get_orders_and_timesteps_for_singlestep_solver
+                ssu, msu = slv.singlestep_dpm_solver_update, slv.multistep_dpm_solver_update
+
+                def w_model(x_, t_):
+                    rec["eval_t"].append(t_.detach().reshape(-1)[:1].clone())
+                    return model(x_, t_)
+
+                def w_gts(*a, **k):
+                    r = gts(*a, **k)
+                    rec.setdefault("first_grid", r.detach().clone())
+                    return r
+
+                def w_gos(*a, **k):
+                    r = gos(*a, **k)
+                    rec["outer"] = r[0].detach().clone()
+                    return r
+
+                def w_ssu(x_, s_, t_, order, **k):
+                    rec["orders"].append(int(order))
+                    return ssu(x_, s_, t_, order, **k)
+
+                def w_msu(x_, ml, tl, t_, order, **k):
+                    rec["orders"].append(int(order))
+                    return msu(x_, ml, tl, t_, order, **k)
+                slv.model, slv.get_time_steps, slv.get_orders_and_timesteps_for_singlestep_solver = w_model, w_gts, w_gos
+                slv.singlestep_dpm_solver_update, slv.multistep_dpm_solver_update = w_ssu, w_msu
+            with torch.no_grad():
+                return slv.sample(x, return_intermediate=inter, **gx.sample_kwargs(case))
+
+        rec = dict(eval_t=[], orders=[])
+        t0 = time.time()
+        out, out64 = run(False, rec), run(True, None)
+        gap = float((out.double() - out64).abs().max())
+        tol = 1e-4 * max(1.0, float(out.abs().max()))
+        eval_t = torch.cat(rec["eval_t"])
+        assert eval_t.dtype == torch.float32
+        outer = rec.get("outer", rec["first_grid"])
+        extra = {}
+        if case["inter"]:
+            out_i, inter = run(False, None, inter=True)
+            assert torch.equal(out_i, out)
+            extra["inter"] = torch.stack(inter)
+        print(f"  {cid}: fp32-fp64 gap {gap:.2e}, max|golden| {float(out.abs().max()):.3g}, tolerance {tol:.2e} -> gap / tolerance = {gap / tol:.3f}; orders {rec['orders']}, "
+              f"{eval_t.numel()} evaluations, {time.time() - t0:.1f}s")
+        if gap > 0.1 * tol:
+            too_noisy.append(cid)
+        save(cid, out=out, out_f64=out64, gap=gap, eval_t=eval_t, orders=np.asarray(rec["orders"], dtype=np.int64), timesteps_outer=outer, cond_chk=chk(cond), **extra)
+    assert not too_noisy, f"the reference's own fp32-fp64 gap exceeds a tenth of the tolerance: change these cases: {too_noisy}"
 
 
 def make_l1ssim(UNetSR3, D, S, net_for):
@@ -785,6 +876,8 @@ def main():
         make_dynthresh(UNetSR3, D, S, net_for)
     if "l1ssim" in only:
         make_l1ssim(UNetSR3, D, S, net_for)
+    if "dpmx" in only:
+        make_dpmx(UNetSR3, D, S, net_for)
 
     if "psnr" in only:
         import importlib.util
