@@ -331,6 +331,14 @@ int ddif_plan_sample_dpm(ddif_plan_t plan, const ddif_dpm_program* prog, const f
     DDIF_GUARD_END
 }
 
+int ddif_plan_sample_dpm_guided(ddif_plan_t plan, const ddif_dpm_program* prog, float guidance_scale, const float* x_T, float clamp_lo, float clamp_hi, int do_clamp,
+                                float* out, float* inter_out, void* stream) {
+    DDIF_GUARD_BEGIN
+    DDIF_PLAN_ENTER(plan, "ddif_plan call");
+    return plan->p.sample_dpm_guided(prog, guidance_scale, x_T, clamp_lo, clamp_hi, do_clamp, out, inter_out, (hipStream_t)stream);
+    DDIF_GUARD_END
+}
+
 int ddif_plan_q_sample_forward(ddif_plan_t plan, const float* x0, const float* noise, const float* sqrt_ac_host,
                                const float* sqrt_1mac_host, const float* time_host, const float* self_cond, float* pred,
                                void* stream) {

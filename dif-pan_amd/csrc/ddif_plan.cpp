@@ -3,6 +3,7 @@
 // 624-666; solver/dpm_solver.py:1179-1221).
 #include "ddif_plan.h"
 #include <algorithm>
+#include <cmath>
 #include "kernels_conv.h"
 #include "kernels_misc.h"
 #include "attn_args.h"
@@ -2337,7 +2338,23 @@ int Plan::sample_dpmpp(const ddif_dpm_tables* t, const float* xT, float lo, floa
 
 // A host-built solver program (include/ddif.h ddif_dpm_program; reference solver/dpm_solver.py:1055-1253).  Validated as a whole before the first launch.
 int Plan::sample_dpm(const ddif_dpm_program* prog, const float* xT, float lo, float hi, int do_clamp, float* out, float* inter_out, hipStream_t s) {
-    if (!cond_set) return fail(DDIF_ERR_STATE, "ddif_plan_sample_dpm before ddif_plan_set_cond");
+    return run_dpm_program(prog, false, 1.f, xT, lo, hi, do_clamp, out, inter_out, s);
+}
+
+// Classifier-free guidance (model_wrapper, solver/dpm_solver.py:330-338): the plan's batch is [unconditional (Bg); conditional (Bg)], the program and its
+// launches are those of sample_dpm at that batch, and dpm_eval_update_kernel combines the two halves of every network output before anything else sees it.
+int Plan::sample_dpm_guided(const ddif_dpm_program* prog, float guidance_scale, const float* xT, float lo, float hi, int do_clamp, float* out, float* inter_out,
+                            hipStream_t s) {
+    if (!prog || !prog->ops || !xT || !out) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm_guided: NULL program, op table, x_T or out");
+    if (!std::isfinite(guidance_scale)) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm_guided: guidance_scale is not finite");
+    if (B % 2) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm_guided: the plan's batch %d is odd -- it holds [unconditional; conditional], two halves of equal size", B);
+    return run_dpm_program(prog, true, guidance_scale, xT, lo, hi, do_clamp, out, inter_out, s);
+}
+
+// guided: xT, out and every inter_out slice hold B / 2 images; state registers hold the same bits in both halves, model registers use their first half only.
+int Plan::run_dpm_program(const ddif_dpm_program* prog, bool guided, float gscale, const float* xT, float lo, float hi, int do_clamp, float* out, float* inter_out,
+                          hipStream_t s) {
+    if (!cond_set) return fail(DDIF_ERR_STATE, "%s before ddif_plan_set_cond", guided ? "ddif_plan_sample_dpm_guided" : "ddif_plan_sample_dpm");
     if (!prog || !prog->ops || prog->n_ops < 1 || !xT || !out) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: NULL program, op table, x_T or out");
     if (prog->algorithm != DDIF_DPM_ALGO_DPMSOLVERPP && prog->algorithm != DDIF_DPM_ALGO_DPMSOLVER)
         return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: algorithm %d (0 dpmsolver++, 1 dpmsolver)", prog->algorithm);
@@ -2390,15 +2407,23 @@ int Plan::sample_dpm(const ddif_dpm_program* prog, const float* xT, float lo, fl
         side_pending = false;
     }
     const int HW = H * W;
-    const size_t n = (size_t)B * HW * C;
+    const int Bo = guided ? B / 2 : B;  // images in x_T, out and an inter_out slice
+    const size_t nfull = (size_t)B * HW * C;
+    const size_t n = (size_t)Bo * HW * C;  // work items of an elementwise launch
+    const size_t half = guided ? n : 0;
     if (need_reg2 && !xreg2)
-        if (int e = dalloc(&xreg2, n)) return e;
+        if (int e = dalloc(&xreg2, nfull)) return e;
     float* const st[DDIF_DPM_NUM_REGS] = {img[0], img[1], xreg2};
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, ew_grid(n), dim3(256), 0, s, xT, B, C, HW, 0, C, img[0]);
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, ew_grid(n), dim3(256), 0, s, xT, Bo, C, HW, 0, C, img[0]);
+    if (guided) hipLaunchKernelGGL(nchw_to_nhwc_kernel, ew_grid(n), dim3(256), 0, s, xT, Bo, C, HW, 0, C, img[0] + half);  // x_in = cat([x, x]) (:334)
     if (int e = time_rows(t_model.data(), (int)t_model.size(), s)) return e;
     QuantArgs qa{};
     if (dyn) {
         qa.a = net_out.p;
+        if (guided) {  // one s_b per guided sample, from the guided noise prediction
+            qa.a2 = net_out.p + half;
+            qa.gscale = gscale;
+        }
         qa.n = (long long)HW * C;
         qa.form = QUANT_DPM;
         qa.pred = pred_mode;
@@ -2421,13 +2446,15 @@ int Plan::sample_dpm(const ddif_dpm_program* prog, const float* xT, float lo, fl
     for (int k = 0; k < prog->n_ops; ++k) {
         const ddif_dpm_op& op = prog->ops[k];
         if (op.kind == DDIF_DPM_EMIT) {
-            hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid(n), dim3(256), 0, s, (const float*)st[op.src], B, C, HW, inter_out + (size_t)emitted * n);
+            hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid(n), dim3(256), 0, s, (const float*)st[op.src], Bo, C, HW, inter_out + (size_t)emitted * n);
             ++emitted;
             continue;
         }
         DpmEvalArgs a{};
         a.n = n;
         a.per = (size_t)HW * C;
+        a.half = half;
+        a.gscale = gscale;
         if (op.kind == DDIF_DPM_UPDATE) {  // an update on its own (the program did not put it behind an evaluation)
             set_update(a, op);
             hipLaunchKernelGGL(dpm_eval_update_kernel, ew_grid(n), dim3(256), 0, s, a);
@@ -2446,7 +2473,7 @@ int Plan::sample_dpm(const ddif_dpm_program* prog, const float* xT, float lo, fl
             q.xt = st[op.src];
             q.alpha = op.alpha;
             q.sigma = op.sigma;
-            quantile_launch(q, B, s);
+            quantile_launch(q, Bo, s);
         }
         a.net = net_out.p;
         a.xe = st[op.src];
@@ -2468,7 +2495,7 @@ int Plan::sample_dpm(const ddif_dpm_program* prog, const float* xT, float lo, fl
         }
         hipLaunchKernelGGL(dpm_eval_update_kernel, ew_grid(n), dim3(256), 0, s, a);
     }
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid(n), dim3(256), 0, s, (const float*)img[0], B, C, HW, out);
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel, ew_grid(n), dim3(256), 0, s, (const float*)img[0], Bo, C, HW, out);
     DDIF_HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2506,21 +2533,21 @@ int Plan::q_sample_forward(const float* x0, const float* noise, const float* a_h
 
 }  // namespace ddif
 
-// TEST-ONLY (include/ddif_testops.h): one launch of dpm_eval_update_kernel on plain arrays
-extern "C" int ddif_dpm_eval_update(const float* net, const float* xe, const float* lms, const float* thr, int64_t n, int64_t per, float alpha, float sigma, float lo, float hi,
-                                    int do_clamp, int model_type, int algorithm, int form, int order, const float* x, const float* m0, const float* m1, const float* m2,
-                                    const float* c_host, float* m_out, float* out, void* stream) {
+// TEST-ONLY (include/ddif_testops.h): one launch of dpm_eval_update_kernel on plain arrays; half != 0 is the guided form (n work items, two halves of n floats)
+static int dpm_eval_update_launch(const char* who, const float* net, const float* xe, const float* lms, const float* thr, int64_t n, int64_t per, int64_t half, float gscale,
+                                  float alpha, float sigma, float lo, float hi, int do_clamp, int model_type, int algorithm, int form, int order, const float* x,
+                                  const float* m0, const float* m1, const float* m2, const float* c_host, float* m_out, float* out, void* stream) {
     using namespace ddif;
     if (n < 1 || per < 1 || (net && !xe) || (net && do_clamp && !lms) || model_type < 0 || model_type > 2 || (!net && !form))
-        return fail(DDIF_ERR_INVALID, "ddif_dpm_eval_update: bad argument");
+        return fail(DDIF_ERR_INVALID, "%s: bad argument", who);
     if (form && (!x || !out || !c_host || (form != DDIF_DPM_FORM_MULTI && form != DDIF_DPM_FORM_LIN1 && form != DDIF_DPM_FORM_LIN2 && form != DDIF_DPM_FORM_TAY3) ||
                  (form == DDIF_DPM_FORM_MULTI && (order < 1 || order > 3))))
-        return fail(DDIF_ERR_INVALID, "ddif_dpm_eval_update: bad update");
+        return fail(DDIF_ERR_INVALID, "%s: bad update", who);
     const int nm = !form ? 0 : form == DDIF_DPM_FORM_MULTI ? order : form == DDIF_DPM_FORM_LIN1 ? 1 : 3;
     const float* m[3] = {m0, m1, m2};
     for (int j = 0; j < nm; ++j) {
         if (!m[j]) m[j] = (net && m_out) ? m_out : nullptr;  // NULL names the value of this launch
-        if (!m[j]) return fail(DDIF_ERR_INVALID, "ddif_dpm_eval_update: model value %d is missing", j);
+        if (!m[j]) return fail(DDIF_ERR_INVALID, "%s: model value %d is missing", who, j);
     }
     DpmEvalArgs a{};
     a.net = net;
@@ -2537,6 +2564,8 @@ extern "C" int ddif_dpm_eval_update(const float* net, const float* xe, const flo
     a.eps_only = algorithm == DDIF_DPM_ALGO_DPMSOLVER;
     a.n = (size_t)n;
     a.per = (size_t)per;
+    a.half = (size_t)half;
+    a.gscale = gscale;
     a.form = !form ? DPM_FORM_NONE : form == DDIF_DPM_FORM_MULTI ? DPM_FORM_MULTI : form == DDIF_DPM_FORM_TAY3 ? DPM_FORM_TAY3 : DPM_FORM_LIN2;
     a.order = order;
     a.x = x;
@@ -2548,4 +2577,17 @@ extern "C" int ddif_dpm_eval_update(const float* net, const float* xe, const flo
     hipLaunchKernelGGL(dpm_eval_update_kernel, ew_grid((size_t)n), dim3(256), 0, (hipStream_t)stream, a);
     DDIF_HIPCHK(hipGetLastError());
     return DDIF_OK;
+}
+extern "C" int ddif_dpm_eval_update(const float* net, const float* xe, const float* lms, const float* thr, int64_t n, int64_t per, float alpha, float sigma, float lo, float hi,
+                                    int do_clamp, int model_type, int algorithm, int form, int order, const float* x, const float* m0, const float* m1, const float* m2,
+                                    const float* c_host, float* m_out, float* out, void* stream) {
+    return dpm_eval_update_launch("ddif_dpm_eval_update", net, xe, lms, thr, n, per, 0, 1.f, alpha, sigma, lo, hi, do_clamp, model_type, algorithm, form, order, x, m0, m1, m2,
+                                  c_host, m_out, out, stream);
+}
+extern "C" int ddif_dpm_eval_update_guided(const float* net, const float* xe, const float* lms, const float* thr, int64_t n_half, int64_t per, float guidance_scale, float alpha,
+                                           float sigma, float lo, float hi, int do_clamp, int model_type, int algorithm, int form, int order, const float* x, const float* m0,
+                                           const float* m1, const float* m2, const float* c_host, float* m_out, float* out, void* stream) {
+    if (!net || !std::isfinite(guidance_scale)) return ddif::fail(DDIF_ERR_INVALID, "ddif_dpm_eval_update_guided: NULL network output or a guidance_scale that is not finite");
+    return dpm_eval_update_launch("ddif_dpm_eval_update_guided", net, xe, lms, thr, n_half, per, n_half, guidance_scale, alpha, sigma, lo, hi, do_clamp, model_type, algorithm,
+                                  form, order, x, m0, m1, m2, c_host, m_out, out, stream);
 }

@@ -341,6 +341,8 @@ struct Plan {
     int sample_dpmpp(const ddif_dpm_tables* t, const float* xT, float lo, float hi, int do_clamp, float* out,
                      hipStream_t s);
     int sample_dpm(const ddif_dpm_program* prog, const float* xT, float lo, float hi, int do_clamp, float* out, float* inter_out, hipStream_t s);
+    int sample_dpm_guided(const ddif_dpm_program* prog, float guidance_scale, const float* xT, float lo, float hi, int do_clamp, float* out, float* inter_out, hipStream_t s);
+    int run_dpm_program(const ddif_dpm_program* prog, bool guided, float gscale, const float* xT, float lo, float hi, int do_clamp, float* out, float* inter_out, hipStream_t s);
     int q_sample_forward(const float* x0, const float* noise, const float* a_h, const float* s_h, const float* t_h,
                          const float* sc, float* pred, hipStream_t s, const ddif_objective_rows* rows = nullptr, float* recon_out = nullptr);
 };

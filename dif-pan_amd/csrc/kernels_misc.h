@@ -918,6 +918,7 @@ __global__ void dpm_update_kernel(DpmUpdArgs a) {
 //   form 3 tay3  D1_0 = c3*(m1 - m0); D1_1 = c4*(m2 - m0); D1 = (c6*D1_0 - c5*D1_1)/c7; D2 = 2*(D1_1 - D1_0)/c7; v = ((c0*x - c1*m0) + c2*D1) - c[8]*D2   (:749-758, 788-797)
 //                c3 = 1/r1, c4 = 1/r2, c5 = r1, c6 = r2, c7 = r2 - r1: true divisions, as the reference divides tensors
 // A leading minus of the reference is folded into the scalar (a - c*d and a + (-c)*d round alike).  m0 / m1 / m2 equal to m_out name the value of this launch.
+// Under classifier-free guidance (DpmEvalArgs::half) the same launch first combines the two halves of the network output into one noise prediction.
 enum { DPM_FORM_NONE = 0, DPM_FORM_MULTI = 1, DPM_FORM_LIN2 = 2, DPM_FORM_TAY3 = 3 };
 struct DpmEvalArgs {
     const float* net;   // network output; null = no evaluation in this launch (an update on its own)
@@ -935,21 +936,35 @@ struct DpmEvalArgs {
     const float* m2;
     float* out;         // the update's result (in place over x is fine: elementwise)
     float c[9];
+    // Classifier-free guidance (ddif_plan_sample_dpm_guided; solver/dpm_solver.py:330-338).  half != 0: net, xe, lms, x and out hold TWO halves of `half`
+    // floats, [unconditional; conditional], the batch the network ran on; n == half work items, thr and the model registers hold one half.  Item i converts
+    // net[i] and net[i + half] against the same xe[i] (both halves of a state register hold the same bits), eps = eps_u + gscale * (eps_c - eps_u), corrects with
+    // the CONDITIONAL sample's lms[i + half] and thr[i / per], and writes its update to out[i] and out[i + half].  No item reads a state value another item
+    // writes, so in place is still fine.
+    size_t half;
+    float gscale;
 };
+// model_wrapper's model_type branch (solver/dpm_solver.py:296-303)
+__device__ __forceinline__ float dpm_eps_of(const DpmEvalArgs& a, float xv, float o) {
+#pragma clang fp contract(off)
+    if (a.model_type == 0) return (xv - a.alpha * o) / a.sigma;
+    if (a.model_type == 1) return o;
+    const float p = a.alpha * o, q = a.sigma * xv;
+    return p + q;
+}
 __device__ __forceinline__ float dpm_model_value(const DpmEvalArgs& a, size_t i) {
 #pragma clang fp contract(off)
-    const float xv = a.xe[i], o = a.net[i];
-    float eps;
-    if (a.model_type == 0) eps = (xv - a.alpha * o) / a.sigma;
-    else if (a.model_type == 1) eps = o;
-    else {
-        const float p = a.alpha * o, q = a.sigma * xv;
-        eps = p + q;
+    const float xv = a.xe[i];
+    float eps = dpm_eps_of(a, xv, a.net[i]);
+    if (a.half) {  // noise_uncond + guidance_scale * (noise - noise_uncond) (:338)
+        const float d = dpm_eps_of(a, xv, a.net[i + a.half]) - eps;
+        const float gd = a.gscale * d;
+        eps = eps + gd;
     }
     if (a.eps_only) return eps;
     float x0 = (xv - a.sigma * eps) / a.alpha;
     if (a.do_clamp) {
-        const float l = a.lms[i];
+        const float l = a.lms[i + a.half];
         x0 = fminf(fmaxf(x0 + l, a.lo), a.hi) - l;
     } else if (a.thr) {
         const float sb = a.thr[i / a.per];
@@ -966,7 +981,10 @@ __global__ void dpm_eval_update_kernel(DpmEvalArgs a) {
             if (a.m_out) a.m_out[i] = mv;
         }
         if (a.form == DPM_FORM_NONE) {
-            if (a.out) a.out[i] = mv;
+            if (a.out) {
+                a.out[i] = mv;
+                if (a.half) a.out[i + a.half] = mv;
+            }
             continue;
         }
         const bool fresh = a.net != nullptr && a.m_out != nullptr;
@@ -1002,6 +1020,7 @@ __global__ void dpm_eval_update_kernel(DpmEvalArgs a) {
             v = (v + a.c[2] * d1) - a.c[8] * d2;
         }
         a.out[i] = v;
+        if (a.half) a.out[i + a.half] = v;
     }
 }
 

@@ -21,6 +21,15 @@ namespace ddif {
 
 enum { QUANT_HDR_BYTES = 2048 };  // hist[256] | ctl[16] | wmin[16] in front of the resident keys
 
+// model_wrapper's model_type branch (solver/dpm_solver.py:296-303) as dpm_x0_kernel evaluates it
+__device__ __forceinline__ float quant_dpm_eps(const QuantArgs& a, float xv, float o) {
+#pragma clang fp contract(off)
+    if (a.pred == 0) return (xv - a.alpha * o) / a.sigma;
+    if (a.pred == 1) return o;
+    const float p = a.alpha * o, q = a.sigma * xv;
+    return p + q;
+}
+
 __device__ __forceinline__ unsigned quant_key(const QuantArgs& a, size_t i, float px, float po) {
 #pragma clang fp contract(off)
     float v;
@@ -31,13 +40,12 @@ __device__ __forceinline__ unsigned quant_key(const QuantArgs& a, size_t i, floa
         if (a.pred) x0 = pred_x0(px, a.xt[i], po, x0);
         v = x0 + a.lms[i];
     } else {  // dpm_x0_kernel up to the corrector
-        const float xv = a.xt[i], o = a.a[i];
-        float eps;
-        if (a.pred == 0) eps = (xv - a.alpha * o) / a.sigma;
-        else if (a.pred == 1) eps = o;
-        else {
-            const float p = a.alpha * o, q = a.sigma * xv;
-            eps = p + q;
+        const float xv = a.xt[i];
+        float eps = quant_dpm_eps(a, xv, a.a[i]);
+        if (a.a2) {  // the guided noise prediction of dpm_eval_update_kernel, in its operand order
+            const float d = quant_dpm_eps(a, xv, a.a2[i]) - eps;
+            const float gd = a.gscale * d;
+            eps = eps + gd;
         }
         v = (xv - a.sigma * eps) / a.alpha;
     }

@@ -18,6 +18,10 @@ struct QuantArgs {
     const SamplerRun* run;  // QUANT_DDPM with pred: tab[6] / tab[7] at *step
     const int* step;
     float alpha, sigma;     // QUANT_DPM
+    // QUANT_DPM under classifier-free guidance (solver/dpm_solver.py:334-338): a = the unconditional half of the network output, a2 = the conditional half
+    // ([B][n] each, B guided samples); x0 comes from eps = eps_u + gscale * (eps_c - eps_u).  a2 == nullptr: no guidance.
+    const float* a2;
+    float gscale;
     // torch.quantile(.., p) (linear): rank r = fp32(p) * fp32(n - 1), order statistics floor(r) and ceil(r), weight r - floor(r)
     long long k_lo, k_hi;
     float w, max_val;

@@ -7,6 +7,7 @@ There is NO fallback path: if the gfx950 library is missing or the tensors are n
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import sys
 import weakref
@@ -132,6 +133,7 @@ class _Lib:
         d.ddif_plan_sample_ddim.argtypes = [vp, C.POINTER(DdimTables), vp, vp, u64, u64, f32, f32, i32, vp, vp]
         d.ddif_plan_sample_dpmpp.argtypes = [vp, C.POINTER(DpmTables), vp, f32, f32, i32, vp, vp]
         d.ddif_plan_sample_dpm.argtypes = [vp, C.POINTER(DpmProgram), vp, f32, f32, i32, vp, vp, vp]
+        d.ddif_plan_sample_dpm_guided.argtypes = [vp, C.POINTER(DpmProgram), f32, vp, f32, f32, i32, vp, vp, vp]
         d.ddif_plan_q_sample_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         d.ddif_plan_set_objective.argtypes = [vp, i32, i32]
         d.ddif_plan_get_objective.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
@@ -762,15 +764,33 @@ class PlanHandle:
     def sample_dpm(self, ops, algorithm: str, x_T: torch.Tensor, clamp):
         """One solver program (ddif_plan_sample_dpm) -> (out, inter): inter stacks one (B,C,H,W) image per "emit" op, or is None without any."""
         self._check_sampler_inputs(x_T, None, 0)
+        return self._run_dpm_program(ops, algorithm, x_T, clamp, None)
+
+    def sample_dpm_guided(self, ops, algorithm: str, guidance_scale: float, x_T: torch.Tensor, clamp):
+        """One solver program under classifier-free guidance (ddif_plan_sample_dpm_guided) -> (out, inter) as sample_dpm.  The plan's batch is 2 * Bg with
+        set_cond(cat([unconditional, conditional])); x_T, out and the intermediates hold Bg images."""
+        _check_tensor(self.lib, x_T, "x_T")
+        if self.B % 2:
+            raise DdifError(f"sample_dpm_guided: the plan's batch {self.B} is odd -- it holds [unconditional; conditional]")
+        _check_shape(x_T, "x_T", (self.B // 2, self.net.out_channel, self.H, self.W))
+        if not math.isfinite(float(guidance_scale)):
+            raise DdifError(f"sample_dpm_guided: guidance_scale {guidance_scale!r} is not finite")
+        return self._run_dpm_program(ops, algorithm, x_T, clamp, float(guidance_scale))
+
+    def _run_dpm_program(self, ops, algorithm, x_T, clamp, guidance_scale):
         x_T = x_T.contiguous()
         prog, keep = self.dpm_program(ops, algorithm)
         n_emit = sum(1 for op in ops if op["kind"] == "emit")
         out = torch.empty_like(x_T)
         inter = torch.empty((n_emit,) + tuple(x_T.shape), dtype=torch.float32, device=x_T.device) if n_emit else None
         lo, hi, do = (clamp[0], clamp[1], 1) if clamp is not None else (0.0, 0.0, 0)
+        dll, stream = self.lib.dll, _stream(self.lib, x_T.device)
         def run():
-            self.lib.check(self.lib.dll.ddif_plan_sample_dpm(self.h, C.byref(prog), _ptr(x_T), lo, hi, do, _ptr(out), _ptr(inter),
-                                                             _stream(self.lib, x_T.device)), "ddif_plan_sample_dpm")
+            if guidance_scale is None:
+                self.lib.check(dll.ddif_plan_sample_dpm(self.h, C.byref(prog), _ptr(x_T), lo, hi, do, _ptr(out), _ptr(inter), stream), "ddif_plan_sample_dpm")
+            else:
+                self.lib.check(dll.ddif_plan_sample_dpm_guided(self.h, C.byref(prog), guidance_scale, _ptr(x_T), lo, hi, do, _ptr(out), _ptr(inter), stream),
+                               "ddif_plan_sample_dpm_guided")
             return out, inter
 
         return self._guarded(run, x_T.device)

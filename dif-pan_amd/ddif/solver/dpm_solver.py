@@ -8,7 +8,13 @@ round trip, the corrector (the image-space clamp or dynamic thresholding, whose 
 kernel in front of the data prediction) and the multistep updates -- is ONE call into libddif (`ddif_plan_sample_dpmpp`)
 when the model is a ddif `UNetSR3`.  Singlestep runs, solver_type="taylor", algorithm_type="dpmsolver", denoise_to_zero
 and return_intermediate are ONE call too (`ddif_plan_sample_dpm`) on a solver program built here: a flat op list over a few
-state and model registers, every scalar the reference's own fp32 expression (`_build_program`).  Any other model / corrector
+state and model registers, every scalar the reference's own fp32 expression (`_build_program`).  Classifier-free guidance
+(`model_wrapper(guidance_scale != 1, unconditional_condition=...)`, reference :330-338) runs the same programs, for every method, through
+`ddif_plan_sample_dpm_guided` on a plan of batch 2B whose cond is `cat([unconditional_condition, condition])`: the network sees the doubled batch
+once per evaluation and the launch behind it combines eps_u + scale * (eps_c - eps_u) before the corrector and the update.  The reference itself
+runs its guided branch with model_type="noise" and B = 1 only (with "x_start" / "v" its (2,)-shaped alpha_t does not broadcast against the doubled
+batch; B > 1 fails the same way everywhere in its solver); here every model type and any B run.  guidance_scale == 1 or no unconditional_condition
+is the single conditional evaluation as before.  Any other model / corrector
 takes the generic loops below (same algorithm, model called per evaluation through the reference's update methods; dynamic
 thresholding there is the stateless `ddif_dynamic_threshold`).  Out of scope and rejected loudly: continuous schedules, the
 adaptive solver (its step size depends on a norm read back from the device every step), classifier guidance (SURVEY.md
@@ -95,8 +101,16 @@ def model_wrapper(model, noise_schedule, model_type="noise", model_kwargs={}, gu
     assert guidance_type in ["uncond", "classifier", "classifier-free"]
     if guidance_type == "classifier":
         raise DdifError("classifier guidance is out of scope of the HIP path")
-    if guidance_type == "classifier-free" and not (guidance_scale == 1.0 or unconditional_condition is None):
-        raise DdifError("classifier-free guidance with scale != 1 is out of scope of the HIP path")
+    guided = guidance_type == "classifier-free" and not (guidance_scale == 1.0 or unconditional_condition is None)  # (:331)
+    if guided:
+        if not math.isfinite(float(guidance_scale)):
+            raise DdifError(f"model_wrapper: guidance_scale {guidance_scale!r} is not finite")
+        if not (torch.is_tensor(condition) and torch.is_tensor(unconditional_condition)):
+            raise DdifError("model_wrapper: classifier-free guidance needs `condition` and `unconditional_condition` tensors")
+        u, c = unconditional_condition, condition
+        if u.shape != c.shape or u.dtype != c.dtype or u.device != c.device:
+            raise DdifError(f"model_wrapper: unconditional_condition ({tuple(u.shape)}, {u.dtype}, {u.device}) does not match condition "
+                            f"({tuple(c.shape)}, {c.dtype}, {c.device}): the network runs once on cat([unconditional_condition, condition])")
 
     def get_model_input_time(t_continuous):
         return (t_continuous - 1.0 / noise_schedule.total_N) * 1000.0  # float model time (:285-286)
@@ -117,10 +131,16 @@ def model_wrapper(model, noise_schedule, model_type="noise", model_kwargs={}, gu
         return -bshape(s, x) * out
 
     def model_fn(x, t_continuous):
-        return noise_pred_fn(x, t_continuous, cond=condition if guidance_type == "classifier-free" else None)
+        if not guided:
+            return noise_pred_fn(x, t_continuous, cond=condition if guidance_type == "classifier-free" else None)
+        x_in = torch.cat([x] * 2)  # one network call on [unconditional; conditional] (:334-338)
+        t_in = torch.cat([t_continuous] * 2)
+        c_in = torch.cat([unconditional_condition, condition])
+        noise_uncond, noise = noise_pred_fn(x_in, t_in, cond=c_in).chunk(2)
+        return noise_uncond + guidance_scale * (noise - noise_uncond)
 
     model_fn.ddif = dict(model=model, noise_schedule=noise_schedule, model_type=model_type, model_kwargs=model_kwargs,
-                         guidance_type=guidance_type, condition=condition)
+                         guidance_type=guidance_type, condition=condition, guidance_scale=guidance_scale, unconditional_condition=unconditional_condition)
     return model_fn
 
 
@@ -243,6 +263,14 @@ class DPM_Solver:
                     torch.equal(cx0.lms, cond[:, :C]):
                 return meta["model"], cond, (cx0.lo, cx0.hi)
         return None
+
+    def _guidance(self):
+        """(guidance_scale, unconditional_condition) when model_wrapper takes its guided branch (reference :333-338), else None (:331-332)."""
+        meta = getattr(self._model_fn, "ddif", None)
+        if meta is None or meta["guidance_type"] != "classifier-free":
+            return None
+        scale, uncond = meta.get("guidance_scale", 1.0), meta.get("unconditional_condition")
+        return None if (scale == 1.0 or uncond is None) else (float(scale), uncond)
 
     # ---- singlestep scalars (reference :555-600, 602-802), fp32 1-element tensors / Python floats exactly as the reference forms them ---------------
     def _first_coefs(self, s, t):
@@ -538,7 +566,7 @@ class DPM_Solver:
         if solver_type not in ("dpmsolver", "taylor"):
             raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
         plain = method == "multistep" and solver_type == "dpmsolver" and self.algorithm_type == "dpmsolver++" and not denoise_to_zero and not return_intermediate
-        if not plain:
+        if not plain or (self._guidance() is not None and self._fused_target() is not None):  # a guided run is a solver program whatever its method
             return self._sample_program(x, steps, t_start, t_end, order, skip_type, method, lower_order_final, denoise_to_zero, solver_type, return_intermediate)
         ns = self.noise_schedule
         t_0 = 1.0 / ns.total_N if t_end is None else t_end
@@ -601,17 +629,22 @@ class DPM_Solver:
         if fused is not None:
             ops = self._build_program(steps, order, skip_type, method, lower_order_final, denoise_to_zero, solver_type, return_intermediate, t_T, t_0)
             model, cond, clamp = fused
+            guidance = self._guidance()
             B, _, H, W = x.shape
-            plan = model.plan_for(B, H, W, x.device)
+            plan = model.plan_for(B if guidance is None else 2 * B, H, W, x.device)  # guided: the network's batch is [unconditional; conditional] (:334-337)
             plan.set_objective(self._model_fn.ddif["model_type"], plan.objective[1])
             if clamp == "dynamic":
                 plan.set_threshold("solver", float(self.dynamic_thresholding_ratio), float(self.thresholding_max_val))
                 clamp = None
             else:
                 plan.set_threshold("off")
-            plan.set_cond(cond)
             with torch.no_grad():
-                out, inter = plan.sample_dpm(ops, self.algorithm_type, x, clamp)
+                if guidance is None:
+                    plan.set_cond(cond)
+                    out, inter = plan.sample_dpm(ops, self.algorithm_type, x, clamp)
+                else:
+                    plan.set_cond(torch.cat([guidance[1], cond]))
+                    out, inter = plan.sample_dpm_guided(ops, self.algorithm_type, guidance[0], x, clamp)
             return (out, list(inter.unbind(0))) if return_intermediate else out
         intermediates = []
         with torch.no_grad():

@@ -199,6 +199,24 @@ typedef struct ddif_dpm_program {
 DDIF_API int ddif_plan_sample_dpm(ddif_plan_t plan, const ddif_dpm_program* prog, const float* x_T, float clamp_lo, float clamp_hi, int do_clamp, float* out,
                                   float* inter_out /* nullable: [number of EMIT ops][B][C][H][W] */, void* stream);
 
+/* The same solver programs under CLASSIFIER-FREE GUIDANCE (model_wrapper, solver/dpm_solver.py:330-338): every evaluation runs the network once on the doubled
+ * batch x_in = cat([x, x]), t_in = cat([t, t]), c_in = cat([unconditional_condition, condition]) (:334-337), converts the whole output to a noise prediction by
+ * the model_type branch (:296-303), and hands on  eps = eps_u + guidance_scale * (eps_c - eps_u)  (:338, in that operation order, contraction off).  Everything
+ * behind it -- data prediction, image-space clamp or dynamic thresholding, every update form, the final denoise, the intermediates -- sees eps as it sees an
+ * unguided noise prediction.
+ *   - The plan's batch is 2 * Bg and ddif_plan_set_cond has been given [unconditional (Bg); conditional (Bg)].  x_T, out and every inter_out slice hold Bg images.
+ *   - x_T is laid into both halves of state register 0; every update writes its result to both halves (they hold the same bits throughout: the network reads a
+ *     state register as its batch); model registers use one half.  EMIT and the final store write one half.
+ *   - The corrector is the CONDITIONAL sample's: the clamp reads the lms channels of the conditional half of cond, and dynamic thresholding computes one s_b per
+ *     guided sample from the guided eps.
+ *   - Launches per evaluation are those of ddif_plan_sample_dpm at the same plan batch: the guidance arithmetic rides in the evaluation launch (and in the
+ *     selection launch of dynamic thresholding).  No host synchronisation.
+ * Fails before anything is enqueued: an odd plan batch, a guidance_scale that is not finite or a NULL prog / x_T / out -> DDIF_ERR_INVALID; cond not set ->
+ * DDIF_ERR_STATE; and the program validation of ddif_plan_sample_dpm.  guidance_scale == 1 is legal here (eps_u + (eps_c - eps_u), not bit-equal to eps_c): the
+ * reference's shortcut to a single conditional evaluation (:331-332) is the caller's, who then uses ddif_plan_sample_dpm on a plan of batch Bg. */
+DDIF_API int ddif_plan_sample_dpm_guided(ddif_plan_t plan, const ddif_dpm_program* prog, float guidance_scale, const float* x_T, float clamp_lo, float clamp_hi,
+                                         int do_clamp, float* out, float* inter_out /* nullable: [number of EMIT ops][Bg][C][H][W] */, void* stream);
+
 /* GaussianDiffusion.p_losses forward half (diffusion/diffusion_ddpm_pan.py:692-732), eval mode, pred_mode x_start:
  * x_t = a[b]*x0 + s[b]*noise; pred = net(x_t, t, cond, self_cond); returns pred (recon_x0). a, s, time: B floats each, HOST or DEVICE
  * memory (copied on `stream`: a training loop that draws t on the device hands them over without a host round trip). */

@@ -116,6 +116,12 @@ DDIF_API int ddif_l1_loss_fwd(const float* pred, const float* target, int64_t n,
 DDIF_API int ddif_dpm_eval_update(const float* net, const float* xe, const float* lms, const float* thr, int64_t n, int64_t per, float alpha, float sigma, float lo, float hi,
                                   int do_clamp, int model_type, int algorithm, int form, int order, const float* x, const float* m0, const float* m1, const float* m2,
                                   const float* c_host, float* m_out, float* out, void* stream);
+/* The guided twin (include/ddif.h ddif_plan_sample_dpm_guided): net, xe, lms, x and out hold 2 * n_half floats, [unconditional; conditional]; thr n_half / per
+ * floats; m0 / m1 / m2 / m_out n_half floats.  Item i reads net[i] and net[i + n_half] against xe[i], combines eps_u + guidance_scale * (eps_c - eps_u), corrects
+ * with lms[i + n_half] / thr[i / per], and writes its update (form 0: its model value) to out[i] and out[i + n_half].  net must not be NULL. */
+DDIF_API int ddif_dpm_eval_update_guided(const float* net, const float* xe, const float* lms, const float* thr, int64_t n_half, int64_t per, float guidance_scale, float alpha,
+                                         float sigma, float lo, float hi, int do_clamp, int model_type, int algorithm, int form, int order, const float* x, const float* m0,
+                                         const float* m1, const float* m2, const float* c_host, float* m_out, float* out, void* stream);
 
 /* ---- the order statistics behind ddif_dynamic_threshold (csrc/kernels_quantile.h) ------------------------------------------
  * x device [B][n]; s_out device [B] = the interpolated quantile of |x_b| (max_val = 0); stats device [B][2] = the two order statistics of |x_b| it

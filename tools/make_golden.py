@@ -15,6 +15,8 @@ written into the repository.
     python tools/make_golden.py --only dpmx                        (DPM-Solver singlestep / singlestep_fixed, solver_type="taylor", algorithm_type="dpmsolver",
                                                                     denoise_to_zero, return_intermediate: tests/golden_cases_dpmx.py; fp32 + fp64 as above,
                                                                     plus orders, outer time steps and the time of every evaluation; not part of the default set)
+    python tools/make_golden.py --only cfg                         (classifier-free guidance in DPM-Solver runs: tests/golden_cases_cfg.py; fp32 + fp64 as above,
+                                                                    plus the time of every evaluation; not part of the default set)
 """
 import argparse
 import json
@@ -458,6 +460,71 @@ def make_dpmx(UNetSR3, D, S, net_for):
     assert not too_noisy, f"the reference's own fp32-fp64 gap exceeds a tenth of the tolerance: change these cases: {too_noisy}"
 
 
+def make_cfg(UNetSR3, D, S, net_for):
+    """Classifier-free guidance in DPM-Solver runs (tests/golden_cases_cfg.py): model_wrapper with guidance_scale != 1 and an unconditional_condition (reference
+    solver/dpm_solver.py:330-338: one network call on [unconditional; conditional]).  As make_dpmx: the reference as it is (fp32: the expected output) and its
+    fp64 twin, schedule scalars in the solver's own fp32 in both; `eval_t` by wrapping the solver's `model`.  `guided_minus_unguided` is the distance to the
+    same run at scale 1: a golden that an unguided run would pass shows nothing."""
+    import copy
+
+    import golden_cases_cfg as gcfg
+    import golden_cases_dpmx as gx
+
+    nets64 = {}
+
+    def net64_for(ds):
+        if ds not in nets64:
+            n = copy.deepcopy(net_for(ds)).double()
+            fwd = n.forward
+            n.forward = lambda x, t, cond=None, self_cond=None: fwd(x.double(), t, None if cond is None else cond.double(), None if self_cond is None else self_cond.double())
+            n.noise_level_mlp[0].register_forward_hook(lambda m, i, o: o.double())
+            nets64[ds] = n
+        return nets64[ds]
+
+    too_noisy = []
+    for case in gcfg.CASES:
+        cid, ds, H, T, seed, mt = case["cid"], case["ds"], case["H"], case["T"], case["seed"], case["model_type"]
+        C = gc.DATASETS[ds][0]
+        cond = gc.tiles_for(ds, 1, H, H, seed=seed)["cond"]
+        uncond = gcfg.unconditional_of(cond, C)
+        xT = torch.randn(1, C, H, H, generator=torch.Generator().manual_seed(seed))
+        betas = torch.as_tensor(D.make_beta_schedule(**gx.schedule_kwargs(case["schedule"], T))).float()
+
+        def run(f64, rec, scale):
+            net = net64_for(ds) if f64 else net_for(ds)
+            cnd, unc, x = (cond.double(), uncond.double(), xT.double()) if f64 else (cond, uncond, xT)
+            ns = S.NoiseScheduleVP("discrete", betas=betas)
+            fn = S.model_wrapper(net, ns, model_type=mt, guidance_type="classifier-free", guidance_scale=scale, condition=cnd, unconditional_condition=unc)
+            lms = cnd[:, :C]
+            corr = {"clamp": lambda x0, t: (x0 + lms).clamp(0, 1.0) - lms, "dyn": "dynamic_thresholding", None: None}[case["corrector"]]
+            slv = S.DPM_Solver(fn, ns, algorithm_type=case["algorithm"], correcting_x0_fn=corr)
+            if rec is not None:
+                model = slv.model
+
+                def w_model(x_, t_):
+                    rec["eval_t"].append(t_.detach().reshape(-1)[:1].clone())
+                    return model(x_, t_)
+                slv.model = w_model
+            with torch.no_grad():
+                return slv.sample(x, **gx.sample_kwargs(case))
+
+        rec = dict(eval_t=[])
+        t0 = time.time()
+        out, out64, plain = run(False, rec, case["scale"]), run(True, None, case["scale"]), run(False, None, 1.0)
+        gap = float((out.double() - out64).abs().max())
+        tol = 1e-4 * max(1.0, float(out.abs().max()))
+        diff = float((out - plain).abs().max())
+        eval_t = torch.cat(rec["eval_t"])
+        assert eval_t.dtype == torch.float32
+        print(f"  {cid}: fp32-fp64 gap {gap:.2e}, max|golden| {float(out.abs().max()):.3g}, tolerance {tol:.2e} -> gap / tolerance = {gap / tol:.3f}; "
+              f"max|guided - unguided| {diff:.3g}, {eval_t.numel()} evaluations, {time.time() - t0:.1f}s")
+        assert diff > 100 * tol, f"{cid}: the guided golden is within {diff:.2e} of the unguided run"
+        if gap > 0.1 * tol:
+            too_noisy.append(cid)
+        save(cid, out=out, out_f64=out64, gap=gap, eval_t=eval_t, guided_minus_unguided=diff, cond_chk=chk(cond))
+    assert not too_noisy, f"the reference's own fp32-fp64 gap exceeds a tenth of the tolerance: change these cases: {too_noisy}"
+
+
 def make_l1ssim(UNetSR3, D, S, net_for):
     """loss_type="l1ssim" (tests/golden_cases_l1ssim.py).  As make_objective, whose twin construction, pinning of t and mask capture this repeats for the one loss:
     the reference as it is (fp32: the expected value) and its fp64 twin with the same fp32 random draws, `<key>_f64` and `gap::<key>` next to every value.
@@ -878,6 +945,8 @@ def main():
         make_l1ssim(UNetSR3, D, S, net_for)
     if "dpmx" in only:
         make_dpmx(UNetSR3, D, S, net_for)
+    if "cfg" in only:
+        make_cfg(UNetSR3, D, S, net_for)
 
     if "psnr" in only:
         import importlib.util
