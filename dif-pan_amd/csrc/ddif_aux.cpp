@@ -17,7 +17,9 @@ struct Scratch {
     size_t n = 0;
 };
 Scratch g_scratch[64];
-int scratch(size_t n, double** out) {
+}  // namespace
+
+int metric_scratch(size_t n, double** out) {  // also the block map of ddif_q2n (ddif_q2n.cpp)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     Scratch& s = g_scratch[dev];
@@ -31,7 +33,6 @@ int scratch(size_t n, double** out) {
     *out = s.p;
     return 0;
 }
-}  // namespace
 
 struct Optim {
     int device = 0;
@@ -73,7 +74,7 @@ int ddif_metrics(const float* gt, const float* pred, int B, int C, int H, int W,
     if (nchunk < 1) nchunk = 1;
     if (nchunk > 64) nchunk = 64;
     double* ws = nullptr;
-    if (int e = ddif::scratch((size_t)B * C * 6 + (size_t)B * nchunk * 2, &ws)) return e;
+    if (int e = ddif::metric_scratch((size_t)B * C * 6 + (size_t)B * nchunk * 2, &ws)) return e;
     double* sums = ws;
     double* part = ws + (size_t)B * C * 6;
     hipStream_t s = (hipStream_t)stream;
@@ -91,7 +92,7 @@ int ddif_ssim(const float* gt, const float* pred, int B, int C, int H, int W, fl
     int nchunk = (n + 255) / 256;
     if (nchunk > 64) nchunk = 64;
     double* part = nullptr;
-    if (int e = ddif::scratch((size_t)B * C * nchunk, &part)) return e;
+    if (int e = ddif::metric_scratch((size_t)B * C * nchunk, &part)) return e;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(ddif::ssim_window_kernel, dim3(nchunk, C, B), dim3(256), 64, s, gt, pred, C, H, W, nchunk, data_range, part);
     hipLaunchKernelGGL(ddif::ssim_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const double*)part, B, C, H, W, nchunk, out);

@@ -119,12 +119,18 @@ def build_model(dataset_name: str, n_steps: int, device, weight_path: Optional[s
     return denoise_fn, diffusion.to(device)
 
 
+def _q2n_cut(gt, sr, division):
+    """(B,) Q2n on the cut the other validation metrics use -- last row and column dropped, as at the reference's commented call site
+    (utils/_metric_legacy.py:300-305) -- of images normalised by `division`."""
+    return _rt.q2n(gt[:, :, :-1, :-1].contiguous(), sr[:, :, :-1, :-1].contiguous(), scale=float(division), block=32, shift=32)
+
+
 @torch.no_grad()
 def test_fn(test_data_path=None, weight_path=None, schedule_type="cosine", batch_size=320, n_steps=1500, show=False,
             device="cuda:0", full_res=False, dataset_name="gf2", division=1023, *, data: Optional[dict] = None,
             state_dict: Optional[dict] = None, sampler: str = "ddim_sample", section_counts: str = "ddim25",
             save_path: Optional[str] = None, seed: Optional[int] = None, tile: Optional[int] = None,
-            x_T: Optional[torch.Tensor] = None):
+            x_T: Optional[torch.Tensor] = None, q2n: bool = False):
     """Reference test_fn (:352-505): same positional / keyword arguments (schedule_type is ignored there too, :408);
     keyword-only extras let it run without h5 files (`data=`), without a checkpoint file (`state_dict=`) and with the
     DDPM sampler (`sampler="ddpm_sample"`).  Returns dict(sr=(N,C,H,W) array in raw units, psnr=[...], metrics=[...]).
@@ -133,7 +139,10 @@ def test_fn(test_data_path=None, weight_path=None, schedule_type="cosine", batch
     on the whole scene by the fused kernel, cut into non-overlapping t x t tiles, the tiles are sampled `batch_size` at a
     time -- sharded over the ranks of the default process group when one is initialised, with one RCCL all-gather per
     batch -- and stitched back.  Noise is keyed by (scene, tile) index, so the result does not depend
-    on batch_size or on the number of GPUs.  `x_T` (tiled mode only, parity tests): (N * tiles, C, t, t) initial noise."""
+    on batch_size or on the number of GPUs.  `x_T` (tiled mode only, parity tests): (N * tiles, C, t, t) initial noise.
+
+    `q2n=True` (new; off by default, the returned dict is then unchanged): when gt is present the dict gains `q2n`, the Q2n index (Q4 / Q8, the metric the
+    paper's tables report; `runtime.q2n`) of every scene, on the cut of the other metrics (last row and column dropped), scale = division, block = shift = 32."""
     if show:
         raise DdifError("show=True (matplotlib grids) is out of scope of this build")
     d = data if data is not None else _load_h5(test_data_path)
@@ -146,7 +155,7 @@ def test_fn(test_data_path=None, weight_path=None, schedule_type="cosine", batch
     _, diffusion = build_model(dataset_name, n_steps, device, weight_path, state_dict, image_size=lms_all.shape[-1])
     if seed is not None:
         torch.manual_seed(seed)
-    preds, scores, mets = [], [], []
+    preds, scores, mets, q2ns = [], [], [], []
     wave_order = 1 if dataset_name in ("cave", "harvard") else 0
     H, W = lms_all.shape[-2:]
     if tile is not None and (H > tile or W > tile):
@@ -169,6 +178,8 @@ def test_fn(test_data_path=None, weight_path=None, schedule_type="cosine", batch
                 gt = gt_all[i:i + 1].to(device)
                 scores.append(psnr(gt.cpu(), sr.cpu()))
                 mets.append(_rt.metrics(gt, sr, 4.0).cpu().numpy())  # SAM / ERGAS / PSNR / CC on the GPU (reference :449)
+                if q2n:
+                    q2ns.append(_q2n_cut(gt, sr, division).cpu().numpy())
             preds.append((sr.cpu().numpy() * division).clip(0, division))
     else:
         # whole scenes through the network, as the reference does (:373-377).  The kernels address a tensor with 32-bit byte offsets: a batch
@@ -194,10 +205,14 @@ def test_fn(test_data_path=None, weight_path=None, schedule_type="cosine", batch
                 gt = gt_all[i:i + bs].to(device)
                 scores.append(psnr(gt.cpu(), sr.cpu()))
                 mets.append(_rt.metrics(gt, sr, 4.0).cpu().numpy())
+                if q2n:
+                    q2ns.append(_q2n_cut(gt, sr, division).cpu().numpy())
             preds.append((sr.cpu().numpy() * division).clip(0, division))
             i += raw_l.shape[0]
     out = dict(sr=np.concatenate(preds, axis=0), psnr=scores,
                metrics=(np.concatenate(mets, axis=0) if mets else np.zeros((0, 4), np.float32)))  # columns: SAM, ERGAS, PSNR (ref. sign), CC
+    if q2n and gt_all is not None:
+        out["q2n"] = np.concatenate(q2ns, axis=0)  # one float64 per scene
     if save_path is not None:
         from scipy.io import savemat
 
@@ -360,7 +375,7 @@ def engine_google(train_dataset_path, valid_dataset_path, dataset_name=None, ima
                   schedule_type="cosine", n_steps=3_000, max_iterations=400_000, device="cuda:0", batch_size=128,
                   lr_d=1e-4, show_recon=False, pretrain_weight=None, pretrain_iterations=None, *, constrain_channel=None,
                   add_n_channel=1, ema_start_iter=20_000, valid_every=5_000, save_dir=None, save_every=5_000, resume_state=None,
-                  data_seed=0, log=print, log_every=1):
+                  data_seed=0, log=print, log_every=1, q2n=False):
     """Reference engine_google (:52-348): the training loop.  Same keyword names and defaults; `train_dataset_path` / `valid_dataset_path`
     may also be dicts {"pan", "lms", "gt"} of raw-count arrays (h5py is not part of this image).  Per iteration, as in the reference
     (:218-241): cond assembly (one kernel), `diff_loss, recon = diffusion(hr - lms, cond=cond)`, `diff_loss.backward()` (the library's
@@ -375,7 +390,9 @@ def engine_google(train_dataset_path, valid_dataset_path, dataset_name=None, ima
     permutation was drawn from); `resume_state=<that file>` continues such a run bit-identically, also from the middle of an epoch.
     `log_every` (not in the reference, default 1 = its behaviour): read the losses back and log every k-th iteration only -- the iteration
     itself never synchronises with the host.  Plotting, tensorboard and .mat dumps of the reference are out of scope.  Returns a dict with the loss history, the validation records,
-    the model, the diffusion wrapper and the EMA weights."""
+    the model, the diffusion wrapper and the EMA weights.  `q2n=True` (not in the reference, whose call is commented out; off by default, the records are then
+    unchanged): every validation record gains "Q2n", the batch mean of `runtime.q2n` (Q4 / Q8) on the cut of the other metrics, scale = division,
+    block = shift = 32."""
     import random as _random
 
     import torch.distributed as dist
@@ -475,7 +492,10 @@ def engine_google(train_dataset_path, valid_dataset_path, dataset_name=None, ima
         gtn = (gt / div).contiguous()
         m = _rt.metrics(gtn, sr.contiguous(), ergas_ratio=4.0).mean(dim=0).cpu()
         ssim = float(_rt.ssim(gtn, sr.contiguous()).mean().cpu())
-        return {"SAM": float(m[0]), "ERGAS": float(m[1]), "PSNR": float(m[2]), "CC": float(m[3]), "SSIM": ssim}
+        rec = {"SAM": float(m[0]), "ERGAS": float(m[1]), "PSNR": float(m[2]), "CC": float(m[3]), "SSIM": ssim}
+        if q2n:
+            rec["Q2n"] = float(_q2n_cut(gtn, sr, div).mean().cpu())
+        return rec
 
     def save(it):
         os.makedirs(save_dir, exist_ok=True)

@@ -160,6 +160,7 @@ class _Lib:
         d.ddif_cond_assemble.argtypes = [vp, vp, f32, i32, i32, i32, i32, i32, i32, vp, vp]
         d.ddif_metrics.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, vp]
         d.ddif_ssim.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, vp]
+        d.ddif_q2n.argtypes = [vp, vp, i32, i32, i32, i32, f32, i32, i32, vp, vp, vp]
         d.ddif_optim_create.argtypes = [C.POINTER(vp), i32, C.POINTER(C.c_int64), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32]
         d.ddif_optim_create_ex.argtypes = [C.POINTER(vp), i32, C.POINTER(C.c_int64), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32]
         d.ddif_optim_destroy.argtypes = [vp]
@@ -935,6 +936,41 @@ def ssim(gt: torch.Tensor, pred: torch.Tensor, data_range: float = 2.0) -> torch
     out = torch.empty((B,), dtype=torch.float32, device=gt.device)
     lib.check(lib.dll.ddif_ssim(_ptr(gt), _ptr(pred), B, Cc, H, W, float(data_range), _ptr(out), _stream(lib, gt.device)), "ddif_ssim")
     return out
+
+
+def q2n(gt: torch.Tensor, pred: torch.Tensor, scale: float = 1.0, block: int = 32, shift: int = 32, return_map: bool = False):
+    """(B,) float64 Q2n per image -- Q4 on four bands, Q8 on eight (include/ddif.h ddif_q2n states the definition): the published index of Garzelli &
+    Nencini, per block of `block` x `block` pixels every `shift` pixels, image value = the mean of the blocks.  gt, pred: (B, C, H, W) float32, 1 <= C <= 8;
+    `scale` takes the images to sensor counts before they are rounded to uint16 (1 for raw units, the dataset's division for normalised images).  With
+    return_map=True returns (q, map) with the (B, ny, nx) float64 block map.  Parity is pinned on the reference's building blocks (norm_blocco, onion_mult,
+    onion_mult2D), not on the return value of its `q2n`, which indexes a column where it means a band (utils/_metric_legacy.py:193)."""
+    lib = get_lib()
+    _check_tensor(lib, gt, "gt")
+    _check_tensor(lib, pred, "pred")
+    _check_current_device(gt, "gt")
+    if gt.dim() != 4 or gt.numel() == 0:
+        raise DdifError(f"gt: expected a non-empty (B, C, H, W) tensor, got shape {tuple(gt.shape)}")
+    _check_shape(pred, "pred", tuple(gt.shape))
+    if pred.device != gt.device:
+        raise DdifError(f"pred is on {pred.device}, gt on {gt.device}")
+    B, Cc, H, W = gt.shape
+    gt, pred = gt.contiguous(), pred.contiguous()
+    block, shift = int(block), int(shift)
+    ny, nx = (-(-H // shift), -(-W // shift)) if shift >= 1 else (1, 1)  # a bad shift is refused by the library, by name
+    q = torch.empty((B,), dtype=torch.float64, device=gt.device)
+    qmap = torch.empty((B, ny, nx), dtype=torch.float64, device=gt.device) if return_map else None
+    lib.check(lib.dll.ddif_q2n(_ptr(gt), _ptr(pred), B, Cc, H, W, float(scale), block, shift, _ptr(qmap), _ptr(q), _stream(lib, gt.device)), "ddif_q2n")
+    return (q, qmap) if return_map else q
+
+
+def q_avg(gt: torch.Tensor, pred: torch.Tensor, scale: float = 1.0, block: int = 32, shift: int = 32) -> torch.Tensor:
+    """(B,) float64: the toolbox's "Q" -- the mean over the bands of the single-band index, i.e. `q2n` of every band on its own (C = 1)."""
+    if gt.dim() != 4 or gt.numel() == 0:
+        raise DdifError(f"gt: expected a non-empty (B, C, H, W) tensor, got shape {tuple(gt.shape)}")
+    _check_shape(pred, "pred", tuple(gt.shape))
+    B, Cc, H, W = gt.shape
+    q = q2n(gt.contiguous().view(B * Cc, 1, H, W), pred.contiguous().view(B * Cc, 1, H, W), scale, block, shift)
+    return q.view(B, Cc).mean(dim=1)
 
 
 class FusedAdamW:

@@ -331,6 +331,31 @@ DDIF_API int ddif_metrics(const float* gt, const float* pred, int B, int C, int 
  * PARITY UNPINNED: skimage is absent from the build image; the oracle restates the published algorithm. */
 DDIF_API int ddif_ssim(const float* gt, const float* pred, int B, int C, int H, int W, float data_range, float* out, void* stream);
 
+/* Q2n quality index per image -- Q4 on four bands, Q8 on eight: the index the paper's tables report next to SAM and ERGAS (Garzelli & Nencini 2009,
+ * as in the pansharpening toolbox that the reference's `q2n` / `onions_quality`, utils/_metric_legacy.py:15-259, were ported from; its call site there is
+ * commented out, :305).  gt, pred: (B, C, H, W) fp32 on the device, 1 <= C <= 8.  All block arithmetic is fp64.
+ *   quantisation  v = rint(min(max(x * scale, 0), 65535)): the multiply in fp32, rounding half to even.  scale = 1 for raw sensor units, the dataset's
+ *                 division for images normalised by it.  ROUNDING RULE: the MATLAB original's uint16() rounds, the Python port's
+ *                 np.array(..., dtype=np.uint16) truncates; the two agree on integer-valued inputs, and this entry point rounds.
+ *   bands         zero bands are appended up to Cp, the next power of two >= C (what :75-79 intends).
+ *   blocks        ny = ceil(H / shift), nx = ceil(W / shift); block (j, i) reads rows j*shift .. j*shift + block - 1 and the matching columns, indices
+ *                 beyond H - 1 / W - 1 clamped (edge replication: what the reference's padding :41-44 does wherever it runs; defined here for every size).
+ *   per block     n = block^2, g_k / f_k the gt / pred bands:
+ *                 s_k = mean(g_k);  t_k = population std of g_k, 1e-8 where that is 0 (norm_blocco, :99-104)
+ *                 a_k = (g_k - s_k) / t_k + 1;   y_k = (f_k - s_k) / t_k + 1, or f_k - s_k + 1 (no division) where s_k == 0 exactly (:146-150)
+ *                 z1 = (a_0, .., a_{Cp-1}), z2 = (y_0, -y_1, .., -y_{Cp-1}), m1 / m2 their per-band means over the block
+ *                 T3 = n/(n-1) (mean|z1|^2 + mean|z2|^2 - |m1|^2 - |m2|^2);   bias = 2 |m1| |m2| / (|m1|^2 + |m2|^2)
+ *                 T3 == 0: q = (0, .., 0, bias);  else q = n/(n-1) (mean(z1 (x) z2) - m1 (x) m2) bias 2 / T3, (x) = the recursion of onion_mult (:228-259)
+ *   results       Q(block) = |q|_2 -> map_out (B, ny, nx) fp64, device, may be NULL;  Q2n(image) = the mean of its blocks -> q_out (B) fp64, device.
+ * The kernel accumulates the integer moments the definition reduces to (exact in 64 bits), so results are bit-identical from run to run and an image's
+ * map does not depend on the batch around it.
+ * PARITY is pinned on the reference's own building blocks (norm_blocco, onion_mult, onion_mult2D, composed as above by tools/make_golden.py), NOT on the
+ * return value of its `q2n`: :193 there takes `qu[:, :, i]` on an (N, bs, bs, C) array -- column i instead of band i -- so that two identical images
+ * score 0.87 .. 2.06 per block instead of 1; it also raises for N > 1, for a band count that is no power of two and for sizes with 2 est > N + 1.
+ * DDIF_ERR_INVALID: gt / pred / q_out NULL, C outside 1..8, block outside 2..64, shift outside 1..block, B / H / W < 1, scale not finite or <= 0. */
+DDIF_API int ddif_q2n(const float* gt, const float* pred, int B, int C, int H, int W, float scale, int block, int shift, double* map_out, double* q_out,
+                      void* stream);
+
 /* Fused optimizer step of the training loop (diffusion_engine.py:237-241): global-norm gradient clipping
  * (utils/misc.py:25-36 -> clip_grad_norm_), torch.optim.AdamW.step and EmaUpdater.update (utils/optim_utils.py:43-58) as
  * three launches over a chunk table, whatever the number of tensors.  The handle owns the moment buffers (zero-initialised);

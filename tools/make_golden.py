@@ -17,6 +17,9 @@ written into the repository.
                                                                     plus orders, outer time steps and the time of every evaluation; not part of the default set)
     python tools/make_golden.py --only cfg                         (classifier-free guidance in DPM-Solver runs: tests/golden_cases_cfg.py; fp32 + fp64 as above,
                                                                     plus the time of every evaluation; not part of the default set)
+    python tools/make_golden.py --only q2n                         (the Q2n index: tests/golden_cases_q2n.py; block values from a composition of the reference's
+                                                                    norm_blocco / onion_mult / onion_mult2D in fp64, with each block's sensitivity to summation
+                                                                    order; not part of the default set)
 """
 import argparse
 import json
@@ -685,6 +688,89 @@ def make_l1ssim(UNetSR3, D, S, net_for):
     assert not too_noisy, f"the reference's own fp32-fp64 gap exceeds a tenth of the tolerance: change the seed or the pinned t of these cases: {too_noisy}"
 
 
+def make_q2n():
+    """The Q2n index (tests/golden_cases_q2n.py; include/ddif.h ddif_q2n states the definition).  The reference's own `q2n` cannot be the oracle: it takes
+    `qu[:, :, i]` on an (N, bs, bs, C) array (utils/_metric_legacy.py:193: a column, not a band), and raises for N > 1, for band counts that are no power
+    of two and for some sizes.  Its building blocks are right, so the expected block values are a composition of ITS norm_blocco, onion_mult and
+    onion_mult2D, imported here, along the definition: bands zero-padded to a power of two, blocks cut with clamped indices (edge replication, which is
+    what its padding does wherever it runs), fp64 throughout.  Per (image pair, block) the file holds Q, the per-band s and t, T3, the bias, and
+    `sens`: the largest change of Q under N_PERMUTATIONS random permutations of the block's pixels -- the composition's own sensitivity to summation
+    order, which the tests scale their tolerance by."""
+    import importlib.util
+
+    import golden_cases_q2n as gq
+
+    spec = importlib.util.spec_from_file_location("_ref_metric_legacy", os.path.join(REF, "utils", "_metric_legacy.py"))
+    R = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(R)
+
+    def block_q(g, f):  # (bs, bs, Cp) fp64 each
+        bs, Cp = g.shape[0], g.shape[-1]
+        n = bs * bs
+        z1, z2 = np.empty_like(g), np.empty_like(f)
+        s, t = np.zeros(Cp), np.zeros(Cp)
+        for k in range(Cp):
+            z1[..., k], s[k], t[k] = R.norm_blocco(g[..., k])
+            y = (f[..., k] - s[k] + 1) if s[k] == 0 else ((f[..., k] - s[k]) / t[k] + 1)
+            z2[..., k] = y if k == 0 else -y
+        m1, m2 = z1.mean(axis=(0, 1)), z2.mean(axis=(0, 1))
+        n1, n2 = (m1 ** 2).sum(), (m2 ** 2).sum()
+        T3 = n / (n - 1) * ((z1 ** 2).sum(axis=-1).mean() + (z2 ** 2).sum(axis=-1).mean() - n1 - n2)
+        bias = 2 * np.sqrt(n1) * np.sqrt(n2) / (n1 + n2)
+        if T3 == 0:
+            q = np.zeros(Cp)
+            q[-1] = bias
+        else:
+            qu = R.onion_mult2D(z1[None], z2[None])[0]
+            q = n / (n - 1) * (qu.mean(axis=(0, 1)) - R.onion_mult(m1.copy(), m2.copy())) * bias * 2 / T3
+        return float(np.sqrt((q ** 2).sum())), s, t, float(T3), float(bias)
+
+    def run(case, gt, preds, regular):
+        name, B, C, H, W, block, shift = case
+        Cp = 1 << (C - 1).bit_length()
+        ny, nx = -(-H // shift), -(-W // shift)
+        prng = np.random.default_rng(4242)
+        arrs = dict(gt=gt, geometry=np.array([B, C, H, W, block, shift, ny, nx]))
+
+        def padded(img):  # (C, H, W) uint16 -> (H, W, Cp) fp64
+            out = np.zeros((H, W, Cp))
+            out[..., :C] = np.transpose(img.astype(np.float64), (1, 2, 0))
+            return out
+
+        for pair, pred in preds.items():
+            qmap, sens, T3, bias = (np.zeros((B, ny, nx)) for _ in range(4))
+            s, t = np.zeros((B, ny, nx, Cp)), np.zeros((B, ny, nx, Cp))
+            for b in range(B):
+                G, F_ = padded(gt[b]), padded(pred[b])
+                for j in range(ny):
+                    rows = np.minimum(j * shift + np.arange(block), H - 1)
+                    for i in range(nx):
+                        cols = np.minimum(i * shift + np.arange(block), W - 1)
+                        g, f = G[np.ix_(rows, cols)], F_[np.ix_(rows, cols)]
+                        qmap[b, j, i], s[b, j, i], t[b, j, i], T3[b, j, i], bias[b, j, i] = block_q(g, f)
+                        gf, ff = g.reshape(-1, Cp), f.reshape(-1, Cp)
+                        for _ in range(gq.N_PERMUTATIONS):
+                            p = prng.permutation(block * block)
+                            sens[b, j, i] = max(sens[b, j, i], abs(block_q(gf[p].reshape(g.shape), ff[p].reshape(f.shape))[0] - qmap[b, j, i]))
+            if regular:  # (the zero bands appended up to Cp have t = 1e-8 by construction: the rule is about the C real ones)
+                assert (t[..., :C] >= 1).all() and (T3 != 0).all(), f"{name}/{pair}: a block of a regular case is degenerate"
+                assert np.isfinite(qmap).all() and (qmap <= 1 + 1e-12).all() and (qmap >= 0).all(), (name, pair)
+            if pair == "identical":
+                assert np.abs(qmap - 1).max() <= 1e-12, (name, float(np.abs(qmap - 1).max()))  # (the composition's own rounding: a few 1e-14 at most)
+            arrs.update({f"pred_{pair}": pred, f"map_{pair}": qmap, f"sens_{pair}": sens, f"s_{pair}": s, f"t_{pair}": t, f"T3_{pair}": T3,
+                         f"bias_{pair}": bias})
+            print(f"  {name}/{pair}: Q2n {qmap.mean(axis=(1, 2))}, order sensitivity <= {sens.max():.2e}")
+        out = gq.path(name)
+        np.savez_compressed(out, **arrs)
+        size = os.path.getsize(out)
+        assert size < 1 << 20, (name, size)
+        print(f"  wrote {os.path.relpath(out, ROOT)} ({size / 1024:.0f} KiB)")
+
+    for case in gq.CASES:
+        run(case, *gq.images(case), regular=True)
+    run(gq.DEGENERATE, *gq.degenerate_images(), regular=False)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="manifest,fwd,fwdbig,trunc,dpmskip,trainfwd,traingrad,sched,ddpm,ddim,dpm,loss,psnr")
@@ -947,6 +1033,8 @@ def main():
         make_dpmx(UNetSR3, D, S, net_for)
     if "cfg" in only:
         make_cfg(UNetSR3, D, S, net_for)
+    if "q2n" in only:
+        make_q2n()
 
     if "psnr" in only:
         import importlib.util
