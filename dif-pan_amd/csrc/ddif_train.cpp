@@ -793,6 +793,7 @@ static int la_check(const char* what, int B, int qd, int H, int W, int heads) {
     if (B < 1 || heads < 1 || qd < heads || qd % heads || H < 1 || W < 1) return ddif::fail(DDIF_ERR_INVALID, "%s: bad argument", what);
     const int d = qd / heads;
     if (d > 32 || d % 4) return ddif::fail(DDIF_ERR_INVALID, "%s: head dim <= 32 and 4 | head dim only", what);
+    if (qd > 4 * ddif::LA_THREADS) return ddif::fail(DDIF_ERR_INVALID, "%s: at most %d channels (one thread per channel quad of a line)", what, 4 * ddif::LA_THREADS);
     if ((H > W ? H : W) * qd > ddif::LA_TILE_MAX) return ddif::fail(DDIF_ERR_INVALID, "%s: max(H, W) * channels must not exceed %d", what, ddif::LA_TILE_MAX);
     return 0;
 }

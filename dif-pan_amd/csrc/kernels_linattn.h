@@ -16,8 +16,13 @@ namespace ddif {
 
 constexpr int LA_THREADS = 256;
 constexpr int LA_TILE_MAX = 8192;  // floats per staged tile (one line of len * C floats must fit)
+// Lines per group: what fits the staged tile, and at most one (line, channel quad) per thread -- la_softmax_tile and la_line_dots give every such pair ONE
+// thread (or P of them), so lines * C / 4 must not exceed the workgroup.  The second limit only binds for lines shorter than 6 pixels with more than
+// 1024 / C of them: never on a square image (there 4 lines x 256 channels is the most), but a 3 x 5 level holds 5 columns of 3 x 256 and a 4 x 8 level 8
+// columns of 4 x 192 -- without it the lines past the 256th pair kept their pre-softmax values.
 __host__ __device__ inline int la_lines(int len, int C, int nlines) {
     int n = 6144 / (len * C);
+    if (n > 4 * LA_THREADS / C) n = 4 * LA_THREADS / C;
     if (n < 1) n = 1;
     return n > nlines ? nlines : n;
 }
