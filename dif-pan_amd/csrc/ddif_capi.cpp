@@ -369,6 +369,13 @@ int ddif_plan_set_threshold(ddif_plan_t plan, int mode, float ratio, float max_v
     DDIF_GUARD_END
 }
 
+int ddif_plan_set_tiling(ddif_plan_t plan, const ddif_tiling* t) {
+    DDIF_GUARD_BEGIN
+    DDIF_PLAN_ENTER(plan, "ddif_plan_set_tiling");
+    return plan->p.set_tiling(t);
+    DDIF_GUARD_END
+}
+
 int ddif_plan_get_threshold(ddif_plan_t plan, int* mode, float* ratio, float* max_val) {
     if (!plan) return ddif::fail(DDIF_ERR_INVALID, "ddif_plan_get_threshold: NULL plan");
     if (mode) *mode = plan->p.thr_mode;
@@ -489,7 +496,7 @@ int ddif_prof_classes(ddif_plan_t plan, ddif_prof_class* out6) {
 
 int ddif_plan_num_launches(ddif_plan_t plan, int* step_launches, int* cond_launches) {
     if (!plan) return ddif::fail(DDIF_ERR_INVALID, "NULL plan");
-    if (step_launches) *step_launches = (int)plan->p.step.size();
+    if (step_launches) *step_launches = (int)plan->p.step.size() + plan->p.step_tail_launches();  // under tiling: + update, fusion, counter
     if (cond_launches) *cond_launches = (int)plan->p.pre.size();
     return DDIF_OK;
 }

@@ -1824,6 +1824,62 @@ int Plan::set_threshold(int mode, float ratio, float max_val) {
     thr_max = max_val;
     return 0;
 }
+// ---- overlapping tiles (include/ddif.h ddif_plan_set_tiling)
+int Plan::set_tiling(const ddif_tiling* t) {
+    if (!t) {
+        if (tiling_on) drop_graphs();  // the captured pair holds the tiled tail
+        tiling_on = false;
+        return 0;
+    }
+    if (t->n_scenes < 1) return fail(DDIF_ERR_INVALID, "ddif_plan_set_tiling: n_scenes %d must be >= 1", t->n_scenes);
+    if (t->overlap < 0 || t->overlap >= std::min(H, W)) return fail(DDIF_ERR_INVALID, "ddif_plan_set_tiling: overlap %d outside [0, min(H, W) = %d)", t->overlap, std::min(H, W));
+    if (t->scene_h < H || t->scene_w < W) return fail(DDIF_ERR_INVALID, "ddif_plan_set_tiling: a scene of %dx%d is smaller than the plan's %dx%d tile", t->scene_h, t->scene_w, H, W);
+    const int ny = ddif_tile_count(t->scene_h, H, t->overlap), nx = ddif_tile_count(t->scene_w, W, t->overlap);
+    if ((long long)t->n_scenes * ny * nx != B)
+        return fail(DDIF_ERR_INVALID, "ddif_plan_set_tiling: %d scenes of %dx%d in %dx%d tiles with overlap %d are %d x %d x %d tiles, the plan's batch is %d", t->n_scenes, t->scene_h,
+                    t->scene_w, H, W, t->overlap, t->n_scenes, ny, nx, B);
+    if (ny > 0x7fff || nx > 0x7fff || (long long)t->scene_h * t->scene_w > 0x7fffffffLL) return fail(DDIF_ERR_INVALID, "ddif_plan_set_tiling: the scene is too large for the tile table");
+    const bool same_geom = ttab.tab && tiling.n_scenes == t->n_scenes && tiling.scene_h == t->scene_h && tiling.scene_w == t->scene_w && tiling.overlap == t->overlap;
+    if (same_geom && tiling_on) return 0;
+    if (!same_geom) {
+        // py | px | ycov | xcov | mpx (tiling_args.h TileTab)
+        std::vector<int> tab;
+        for (int k = 0; k < ny; ++k) tab.push_back(ddif_tile_origin(k, t->scene_h, H, t->overlap));
+        for (int k = 0; k < nx; ++k) tab.push_back(ddif_tile_origin(k, t->scene_w, W, t->overlap));
+        auto covers = [&](int L, int tl, int n, int off) {
+            for (int y = 0; y < L; ++y) {
+                int first = 0, cnt = 0;
+                for (int k = 0; k < n; ++k)
+                    if (tab[off + k] <= y && y < tab[off + k] + tl) {
+                        if (!cnt) first = k;
+                        ++cnt;
+                    }
+                tab.push_back(first | (cnt << 16));
+            }
+        };
+        covers(t->scene_h, H, ny, 0);
+        covers(t->scene_w, W, nx, ny);
+        const int* ycov = tab.data() + ny + nx;
+        int npx = 0;
+        for (int y = 0; y < t->scene_h; ++y)
+            for (int x = 0; x < t->scene_w; ++x)
+                if ((ycov[y] >> 16) * (ycov[t->scene_h + x] >> 16) > 1) ++npx;
+        tab.reserve(tab.size() + npx);
+        for (int y = 0; y < t->scene_h; ++y)
+            for (int x = 0; x < t->scene_w; ++x) {
+                const int cy = tab[ny + nx + y] >> 16, cx = tab[ny + nx + t->scene_h + x] >> 16;
+                if (cy * cx > 1) tab.push_back(y * t->scene_w + x);
+            }
+        int* d = nullptr;
+        if (int e = dalloc(&d, tab.size())) return e;  // a new table: work in flight may still read the old one, which stays in `allocs` until destroy
+        DDIF_HIPCHK(hipMemcpy(d, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+        ttab = TileTab{d, t->n_scenes, t->scene_h, t->scene_w, H, W, ny, nx, npx};
+        tiling = *t;
+    }
+    drop_graphs();  // the captured pair holds the other tail / the other table
+    tiling_on = true;
+    return 0;
+}
 // device copies of the caller's per-sample rows (host or device source, like sqrt_ac / sqrt_1mac)
 int Plan::objective_rows(const ddif_objective_rows* rows, bool need_p2, hipStream_t s) {
     const bool need_rec = pred_mode != DDIF_PRED_X_START;
@@ -2012,6 +2068,9 @@ int Plan::range_status(hipStream_t s, int* overflow) {
     return 0;
 }
 
+static const char* const TILING_NO_SOLVER =
+    "the plan is tiled (ddif_plan_set_tiling) and per-step fusion inside solver programs is not implemented -- turn tiling off, sample the tiles independently and blend "
+    "them once at the end (\"final\" blending, ddif_tiles_blend)";
 static int check_sampler_net(const Net* n) {
     if (n->cfg.in_channel != n->cfg.out_channel)
         return fail(DDIF_ERR_INVALID, "samplers need in_channel == out_channel (x_start prediction over the image channels)");
@@ -2024,6 +2083,8 @@ static int check_sampler_net(const Net* n) {
 int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int n_tabs, const ddif_pred_tables* pred_tabs, const float* t_model, const float* xT,
                       const float* noise, uint64_t seed, uint64_t tile0, float lo, float hi, int do_clamp, float* out, hipStream_t s) {
     if (int e = check_sampler_net(net)) return e;
+    if (tiling_on && kind == 0 && thr_mode == DDIF_THRESHOLD_DDPM)
+        return fail(DDIF_ERR_INVALID, "ddif_plan_sample_ddpm: dynamic thresholding (ddif_plan_set_threshold mode 1) under tiling -- the per-tile s_b would differ between the covers of a pixel");
     if (side_pending) {  // a train-mode plan: the cond-only side work must not be waited for inside a captured step
         train_join(s);
         side_pending = false;
@@ -2031,6 +2092,7 @@ int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int 
     const int HW = H * W;
     const size_t n = (size_t)B * HW * C;
     if (xT) hipLaunchKernelGGL(nchw_to_nhwc_kernel, ew_grid(n), dim3(256), 0, s, xT, B, C, HW, 0, C, img[0]);
+    else if (tiling_on) randn_tiled_launch(img[0], C, ttab, (unsigned long long)seed, 0u, (unsigned long long)tile0, s);  // keyed by scene pixel: every cover draws the same normal
     else hipLaunchKernelGGL(randn_nhwc_kernel, ew_grid(n), dim3(256), 0, s, img[0], B, C, HW, (unsigned long long)seed, 0u, (unsigned long long)tile0);
     if (int e = time_rows(t_model, n_steps, s)) return e;
     if (!d_step) {
@@ -2070,7 +2132,8 @@ int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int 
     // dynamically): s_b needs the whole sample, which the final conv's epilogue cannot see -> the unfused tail with the quantile kernel in front of the update
     const bool dyn = thr_mode == DDIF_THRESHOLD_DDPM && kind == 0 && do_clamp;
     if (kind == 0 && graph_exec[0] && graph_dyn != dyn) drop_graphs();
-    const bool fused = !dyn && (pred ? final_fused_pred : final_fused);
+    // tiling: the fusion needs x_{t-1} of every cover, which the final conv's epilogue of one tile cannot see -> the unfused tail as well, the fusion behind the update
+    const bool fused = !dyn && !tiling_on && (pred ? final_fused_pred : final_fused);
     QuantArgs qa{};
     if (dyn) {
         qa.a = net_out.p;
@@ -2120,8 +2183,10 @@ int Plan::run_sampler(int kind, int n_steps, const float* const* tabs_host, int 
             quantile_launch(q, B, st);
             a.thr = d_thr;
         }
+        if (tiling_on) a.tile = ttab;
         if (kind == 0) hipLaunchKernelGGL(ddpm_step_kernel, ew_grid(n), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(ddim_step_kernel, ew_grid(n), dim3(256), 0, st, a);
+        if (tiling_on) tile_fuse_launch(img[parity ^ 1], C, ttab, st);
         hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, st, (const int*)(d_step + parity), d_step + (parity ^ 1));
     };
 
@@ -2265,6 +2330,7 @@ int Plan::sample_dpmpp(const ddif_dpm_tables* t, const float* xT, float lo, floa
     if (!t || t->n_evals < 1 || t->order < 1 || t->order > 3 || !t->t_model || !t->alpha || !t->sigma || !t->ord || !t->cx || !t->a_phi1 || !xT || !out)
         return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpmpp: bad tables");
     if (int e = check_sampler_net(net)) return e;
+    if (tiling_on) return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpmpp: %s", TILING_NO_SOLVER);
     const bool dyn = thr_mode == DDIF_THRESHOLD_SOLVER;
     if (dyn && do_clamp)
         return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpmpp: the plan thresholds dynamically (ddif_plan_set_threshold mode 2) -- the image-space clamp is the other corrector, not an addition");
@@ -2359,6 +2425,7 @@ int Plan::run_dpm_program(const ddif_dpm_program* prog, bool guided, float gscal
     if (prog->algorithm != DDIF_DPM_ALGO_DPMSOLVERPP && prog->algorithm != DDIF_DPM_ALGO_DPMSOLVER)
         return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: algorithm %d (0 dpmsolver++, 1 dpmsolver)", prog->algorithm);
     if (int e = check_sampler_net(net)) return e;
+    if (tiling_on) return fail(DDIF_ERR_INVALID, "%s: %s", guided ? "ddif_plan_sample_dpm_guided" : "ddif_plan_sample_dpm", TILING_NO_SOLVER);
     const bool dyn = thr_mode == DDIF_THRESHOLD_SOLVER;
     if (dyn && do_clamp)
         return fail(DDIF_ERR_INVALID, "ddif_plan_sample_dpm: the plan thresholds dynamically (ddif_plan_set_threshold mode 2) -- the image-space clamp is the other corrector, not an addition");

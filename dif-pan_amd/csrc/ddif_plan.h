@@ -4,6 +4,7 @@
 #include <string>
 #include <memory>
 #include "ddif_net.h"
+#include "tiling_args.h"
 
 namespace ddif {
 
@@ -217,6 +218,14 @@ struct Plan {
     float* d_thr = nullptr;             // [B] per-sample s of the current step, written by quantile_abs_kernel (kernels_quantile.h), read by the step kernel behind it
     bool graph_dyn = false;             // the captured DDPM pair holds the thresholding tail (unfused: quantile, update, counter)
     int set_threshold(int mode, float ratio, float max_val);
+    // overlapping tiles (ddif_plan_set_tiling; sticky): the batch is the tiles of tiling.n_scenes scenes; the DDPM / DDIM loops take the unfused tail, fuse the
+    // overlaps behind every update (kernels_tiling.h) and key the library's noise by scene pixel.  The device table stays allocated when tiling goes off, so
+    // that a caller that alternates between one geometry and none allocates once.
+    bool tiling_on = false;
+    ddif_tiling tiling{};
+    TileTab ttab{};                     // geometry + device table of `tiling` (valid while tiling_on, kept afterwards for reuse)
+    int set_tiling(const ddif_tiling* t);
+    int step_tail_launches() const { return tiling_on ? 2 + (ttab.npx > 0 ? 1 : 0) : 0; }
     bool final_fused = false;           // the final conv carries the sampler epilogue: no separate update / counter launches in the DDPM / DDIM loops
     int math_mode = 0;                  // g_math_mode / g_f16_raw at creation: one plan is built under ONE arithmetic even when the process-wide switches change while it builds
     int f16_raw = 1;

@@ -5,6 +5,7 @@
 #pragma once
 #include "ddif_dev.h"
 #include "sampler_dev.h"
+#include "tiling_args.h"
 
 namespace ddif {
 
@@ -780,6 +781,7 @@ struct StepArgs {
     const int* step;
     int pred;          // 1: x0 holds the noise / v prediction -> pred_x0 with tables 6 / 7 in front of the clamp (:369-375); 0: x_start
     const float* thr;  // DDPM, dynamic thresholding (:327-344, 397-398): per-sample s_b = max(quantile(|x0 + lms|, p), max_val) from quantile_abs_kernel, or null = the absolute clamp
+    TileTab tile;      // tile.tab != null: the batch is the tiles of overlapping scenes (ddif_plan_set_tiling) and the library's noise is keyed by scene pixel
 };
 __global__ void step_advance_kernel(const int* cur, int* next) { *next = *cur + 1; }  // double-buffered counters: nobody reads `next` during this step
 
@@ -809,7 +811,7 @@ __global__ void ddpm_step_kernel(StepArgs a) {
             }
         }
         const size_t e = (b * a.C + c) * a.HW + p;
-        const float z = noise ? noise[e] : philox_normal(r.seed, (unsigned)(k + 1), (r.tile0 * a.C * a.HW) + e);
+        const float z = noise ? noise[e] : philox_normal(r.seed, (unsigned)(k + 1), a.tile.tab ? tile_noise_key(a.tile, r.tile0, a.C, b, c, p) : (r.tile0 * a.C * a.HW) + e);
         const float mean = c1 * x0 + c2 * a.img[i];
         a.out[i] = mean + c3 * z;
     }
@@ -840,7 +842,7 @@ __global__ void ddim_step_kernel(StepArgs a) {
         float v = x0 * sqrt_ap + dir_coef * eps;
         if (sigma != 0.f) {
             const size_t e = (b * a.C + c) * a.HW + p;
-            const float z = noise ? noise[e] : philox_normal(r.seed, (unsigned)(k + 1), (r.tile0 * a.C * a.HW) + e);
+            const float z = noise ? noise[e] : philox_normal(r.seed, (unsigned)(k + 1), a.tile.tab ? tile_noise_key(a.tile, r.tile0, a.C, b, c, p) : (r.tile0 * a.C * a.HW) + e);
             v += sigma * z;
         }
         a.out[i] = v;

@@ -199,7 +199,7 @@ class GaussianDiffusion(nn.Module):
             self.register_buffer(k, to_torch(v))
 
     # ------------------------------------------------------------------------------------------------ helpers
-    def _plan(self, cond: torch.Tensor, train: bool = False):
+    def _plan(self, cond: torch.Tensor, train: bool = False, tiling=None):
         if not self.conditional:
             raise DdifError("unconditional sampling is not implemented by the HIP path")
         B, _, H, W = cond.shape
@@ -211,6 +211,7 @@ class GaussianDiffusion(nn.Module):
             plan.set_threshold("ddpm", float(self.dynamic_thresholding_ratio), float(self.thresholding_max_val))
         else:
             plan.set_threshold("off")
+        plan.set_tiling(tiling)  # sticky too: None (every caller but the tiled samplers) turns it off
         plan.set_cond(cond)
         return plan
 
@@ -284,16 +285,20 @@ class GaussianDiffusion(nn.Module):
     # ------------------------------------------------------------------------------------------------ DDPM
     @torch.no_grad()
     def p_sample_loop(self, x_in, continous=False, get_interm_fm=False, *, x_T=None, noise=None, seed=None, tile0=0,
-                      device_rng=False):
+                      device_rng=False, tiling=None):
         """Reference :445-507.  `x_in` is cond.  Extra keyword-only arguments (not in the reference):
         x_T (B,C,H,W) and noise (T,B,C,H,W) in execution order pin the random stream (parity tests); otherwise
         x_T is drawn with torch.randn on the device and the per-step noise comes from the library's counter-based
         generator seeded from torch's RNG.  device_rng=True also draws x_T from that generator, keyed by global tile
-        index `tile0 + b` (tile-sharded runs reproduce the single-GPU result whatever the split)."""
+        index `tile0 + b` (tile-sharded runs reproduce the single-GPU result whatever the split).
+        tiling=(n_scenes, scene_h, scene_w, overlap): the batch is the tiles of overlapping scenes (ddif.sharding.tile_grid); the overlaps are fused after
+        every step and the library's noise is keyed by scene pixel, `tile0` counting scenes (PlanHandle.set_tiling).  A torch-drawn x_T would differ between
+        the covers of a pixel, so x_T is then drawn by the library unless given."""
         if get_interm_fm:
             raise DdifError("get_interm_fm is not supported")
         cond = x_in
-        plan = self._plan(cond)
+        device_rng = device_rng or tiling is not None
+        plan = self._plan(cond, tiling=tiling)
         B, _, H, W = cond.shape
         dev = cond.device
         T = self.num_timesteps
@@ -367,14 +372,15 @@ class GaussianDiffusion(nn.Module):
 
     @torch.no_grad()
     def ddim_sample_loop(self, x_in, section_counts="ddim300", eta=0.0, *, x_T=None, noise=None, seed=None, tile0=0,
-                         clip_denoised=False, device_rng=False):
+                         clip_denoised=False, device_rng=False, tiling=None):
         """Reference :623-666 (+ ddim_sample :594-621).  Respaces the schedule IN PLACE, feeds the respaced index as
-        the timestep and applies no clamp -- all as the reference does."""
+        the timestep and applies no clamp -- all as the reference does.  `tiling`: as in p_sample_loop."""
         assert isinstance(x_in, torch.Tensor)
         use = self.space_timesteps(self.num_timesteps, section_counts)
         self.space_new_betas(use)
         cond = x_in
-        plan = self._plan(cond)
+        device_rng = device_rng or tiling is not None
+        plan = self._plan(cond, tiling=tiling)
         B, _, H, W = cond.shape
         dev = cond.device
         N = len(self.betas)

@@ -26,7 +26,7 @@ from . import runtime as _rt
 from .diffusion.diffusion_ddpm_pan import GaussianDiffusion, make_beta_schedule
 from .models.sr3_dwt import UNetSR3
 from .runtime import DdifError
-from .sharding import cut_tiles, sample_sharded, stitch_tiles
+from .sharding import blend_tiles, cut_tiles, sample_sharded, stitch_tiles, tile_grid
 from .solver.dpm_solver import ImageSpaceClamp
 
 DIVISION = {"wv3": 2047.0, "gf2": 1023.0, "qb": 2047.0, "cave": 1.0, "harvard": 1.0}  # diffusion_engine.py:107
@@ -130,7 +130,7 @@ def test_fn(test_data_path=None, weight_path=None, schedule_type="cosine", batch
             device="cuda:0", full_res=False, dataset_name="gf2", division=1023, *, data: Optional[dict] = None,
             state_dict: Optional[dict] = None, sampler: str = "ddim_sample", section_counts: str = "ddim25",
             save_path: Optional[str] = None, seed: Optional[int] = None, tile: Optional[int] = None,
-            x_T: Optional[torch.Tensor] = None, q2n: bool = False):
+            x_T: Optional[torch.Tensor] = None, q2n: bool = False, overlap: int = 0, fuse: str = "step"):
     """Reference test_fn (:352-505): same positional / keyword arguments (schedule_type is ignored there too, :408);
     keyword-only extras let it run without h5 files (`data=`), without a checkpoint file (`state_dict=`) and with the
     DDPM sampler (`sampler="ddpm_sample"`).  Returns dict(sr=(N,C,H,W) array in raw units, psnr=[...], metrics=[...]).
@@ -140,6 +140,16 @@ def test_fn(test_data_path=None, weight_path=None, schedule_type="cosine", batch
     time -- sharded over the ranks of the default process group when one is initialised, with one RCCL all-gather per
     batch -- and stitched back.  Noise is keyed by (scene, tile) index, so the result does not depend
     on batch_size or on the number of GPUs.  `x_T` (tiled mode only, parity tests): (N * tiles, C, t, t) initial noise.
+
+    `overlap=o` (new, with `tile=t`; 0 = the path above, untouched): the tiles overlap by o pixels on the grid of `sharding.tile_grid` -- any scene with
+    H, W >= t, the last row / column of tiles shifted flush with the border -- and are fused with the blend window of `sharding.blend_tiles`:
+      fuse="step"   (default) the overlaps of x_{t-1} are fused after EVERY denoising step inside the library, with one noise field per scene, so all tiles
+                    covering a pixel stay on one trajectory (no seam, no blur).  All tiles of a scene run in one plan (`batch_size` only groups whole scenes);
+                    a scene whose tiles exceed the 4 GiB activation limit of a plan raises DdifError.  With a process group, rank r takes the scenes
+                    i % world == r and the finished scenes are all-gathered once.  `x_T`: per tile, cut from a scene-sized field by the caller.
+      fuse="final"  the tiles are sampled independently, exactly as with overlap=0 (sharded over the ranks by `sample_sharded`), and blended once at the
+                    end: the mode for scenes whose tiles are split over ranks or do not fit one plan.
+    Noise is keyed by scene (step) or by (scene, tile) (final), so the result does not depend on batch_size or on the number of GPUs.
 
     `q2n=True` (new; off by default, the returned dict is then unchanged): when gt is present the dict gains `q2n`, the Q2n index (Q4 / Q8, the metric the
     paper's tables report; `runtime.q2n`) of every scene, on the cut of the other metrics (last row and column dropped), scale = division, block = shift = 32."""
@@ -158,7 +168,76 @@ def test_fn(test_data_path=None, weight_path=None, schedule_type="cosine", batch
     preds, scores, mets, q2ns = [], [], [], []
     wave_order = 1 if dataset_name in ("cave", "harvard") else 0
     H, W = lms_all.shape[-2:]
-    if tile is not None and (H > tile or W > tile):
+    if overlap and tile is None:
+        raise DdifError("overlap needs tile=")
+    if fuse not in ("step", "final"):
+        raise DdifError(f"fuse={fuse!r}: expected 'step' or 'final'")
+    if tile is not None and overlap:
+        try:
+            ys, xs = tile_grid(H, W, tile, overlap)
+        except ValueError as e:
+            raise DdifError(f"test_fn(tile={tile}, overlap={overlap}) on a {H}x{W} scene: {e}") from e
+        per = len(ys) * len(xs)
+        N = lms_all.shape[0]
+        mode_kw = dict(section_counts=section_counts) if sampler == "ddim_sample" else {}
+        base_seed = 0 if seed is None else seed
+        import torch.distributed as dist
+
+        world = dist.get_world_size() if dist.is_initialized() else 1
+        rank = dist.get_rank() if dist.is_initialized() else 0
+
+        def scene_cond(lo, hi):
+            raw_l, raw_p = lms_all[lo:hi].to(device), pan_all[lo:hi].to(device)
+            return _rt.cond_assemble(raw_l, raw_p, float(division), wave_order)
+
+        srs = [None] * N
+        if fuse == "step":
+            # one plan holds all tiles of its scenes; a rank's scenes are contiguous only without a process group, so only then are they grouped
+            group = max(1, batch_size // per) if world == 1 else 1
+            mine = list(range(rank, N, world))
+            for g0 in range(0, len(mine), group):
+                idx = mine[g0:g0 + group]
+                cond_t = cut_tiles(scene_cond(idx[0], idx[-1] + 1), tile, overlap)
+                xt = None if x_T is None else x_T[idx[0] * per:(idx[-1] + 1) * per].to(device)
+                try:
+                    res = diffusion(cond_t, mode=sampler, seed=base_seed, tile0=idx[0], x_T=xt, tiling=(len(idx), H, W, overlap), **mode_kw)
+                except DdifError as e:
+                    if "4 GiB" in str(e):
+                        raise DdifError(f"test_fn(fuse='step'): the {len(idx) * per} tiles of {len(idx)} scene(s) of {H}x{W} exceed the 4 GiB activation limit of "
+                                        f"one plan; per-step fusion needs all tiles of a scene in one plan -- use fuse='final' (or a smaller batch_size)") from e
+                    raise
+                sr_t = (res + cond_t[:, :C]).clip(0, 1)  # reference :446-447; the covers of a pixel agree bit for bit, so the blend below copies
+                sc = blend_tiles(sr_t, H, W, overlap, n_scenes=len(idx))
+                for k, i in enumerate(idx):
+                    srs[i] = sc if len(idx) == 1 else sc[k]
+            if world > 1:  # one all-gather of the finished scenes: rank r's block holds scenes r, r + world, ..., zero-padded to the longest block
+                n_blk = -(-N // world)
+                blk = torch.zeros((n_blk, C, H, W), dtype=torch.float32, device=device)
+                for j, i in enumerate(mine):
+                    blk[j] = srs[i]
+                allb = torch.empty((world * n_blk, C, H, W), dtype=torch.float32, device=device)
+                dist.all_gather_into_tensor(allb, blk)
+                for i in range(N):
+                    srs[i] = allb[(i % world) * n_blk + i // world]
+        else:
+            for i in range(N):
+                tiles = cut_tiles(scene_cond(i, i + 1), tile, overlap)
+                out_tiles = []
+                for j in range(0, per, batch_size):
+                    xt = None if x_T is None else x_T[i * per + j: i * per + j + batch_size].to(device)
+                    out_tiles.append(sample_sharded(diffusion, tiles[j:j + batch_size].contiguous(), mode=sampler, seed=base_seed, x_T=xt,
+                                                    tile_base=i * per + j, **mode_kw))
+                srs[i] = blend_tiles(torch.cat(out_tiles, dim=0), H, W, overlap).clip(0, 1)
+        for i in range(N):
+            sr = srs[i].unsqueeze(0)
+            if gt_all is not None:
+                gt = gt_all[i:i + 1].to(device)
+                scores.append(psnr(gt.cpu(), sr.cpu()))
+                mets.append(_rt.metrics(gt, sr, 4.0).cpu().numpy())
+                if q2n:
+                    q2ns.append(_q2n_cut(gt, sr, division).cpu().numpy())
+            preds.append((sr.cpu().numpy() * division).clip(0, division))
+    elif tile is not None and (H > tile or W > tile):
         if H % tile or W % tile:
             raise DdifError(f"scene {H}x{W} is not a multiple of tile={tile}")
         ny, nx = H // tile, W // tile

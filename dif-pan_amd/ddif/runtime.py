@@ -79,6 +79,10 @@ LOSS_TYPES = {"l1": 0, "l2": 1, "l1ssim": 2}  # include/ddif.h DDIF_LOSS_*
 THRESHOLD_MODES = {"off": 0, "ddpm": 1, "solver": 2}  # include/ddif.h DDIF_THRESHOLD_*
 
 
+class Tiling(C.Structure):  # include/ddif.h ddif_tiling
+    _fields_ = [("n_scenes", C.c_int32), ("scene_h", C.c_int32), ("scene_w", C.c_int32), ("overlap", C.c_int32)]
+
+
 class ProfResult(C.Structure):
     _fields_ = [("launches", C.c_int64), ("total_ms", C.c_double), ("total_flop", C.c_double),
                 ("total_bytes", C.c_double), ("kernel_name", C.c_char * 128), ("steps_recorded", C.c_int64),
@@ -140,6 +144,9 @@ class _Lib:
         d.ddif_plan_set_threshold.argtypes = [vp, i32, f32, f32]
         d.ddif_plan_get_threshold.argtypes = [vp, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32)]
         d.ddif_dynamic_threshold.argtypes = [vp, i32, C.c_int64, f32, f32, i32, vp, vp, vp]
+        d.ddif_plan_set_tiling.argtypes = [vp, C.POINTER(Tiling)]
+        d.ddif_tiles_cut.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
+        d.ddif_tiles_blend.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
         d.ddif_l1ssim_loss.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, vp, vp, vp]
         d.ddif_plan_sample_ddpm_ex.argtypes = [vp, C.POINTER(DdpmTables), C.POINTER(PredTables), vp, vp, u64, u64, f32, f32, i32, vp, vp]
         d.ddif_plan_sample_ddim_ex.argtypes = [vp, C.POINTER(DdimTables), C.POINTER(PredTables), vp, vp, u64, u64, f32, f32, i32, vp, vp]
@@ -401,6 +408,7 @@ class PlanHandle:
         self.net_out_channels = net.out_channel
         self.objective = ("x_start", "l1")
         self.threshold = ("off", 0.0, 1.0)
+        self.tiling = None
 
     def _create(self):
         h = C.c_void_p()
@@ -426,6 +434,23 @@ class PlanHandle:
         if thr[0] != "off":  # ... and its thresholding
             self.threshold = ("off", 0.0, 1.0)
             self.set_threshold(*thr)
+        til = getattr(self, "tiling", None)
+        if til is not None:  # ... and its tiling
+            self.tiling = None
+            self.set_tiling(til)
+
+    def set_tiling(self, tiling=None):
+        """Overlapping tiles with per-step fusion (include/ddif.h ddif_plan_set_tiling; sticky): tiling = (n_scenes, scene_h, scene_w, overlap) declares
+        the B batch entries to be the tiles of n_scenes scenes on the grid of ddif.sharding.tile_grid (tile = this plan's H x W); None turns it off.  Under it
+        sample_ddpm / sample_ddim fuse the overlaps after every step and key the library's noise by scene pixel (tile0 then counts scenes)."""
+        if tiling is not None:
+            tiling = tuple(int(v) for v in tiling)
+            if len(tiling) != 4:
+                raise DdifError(f"tiling {tiling!r}: expected (n_scenes, scene_h, scene_w, overlap) or None")
+        if tiling != self.tiling:
+            st = None if tiling is None else Tiling(*tiling)
+            self.lib.check(self.lib.dll.ddif_plan_set_tiling(self.h, None if st is None else C.byref(st)), "ddif_plan_set_tiling")
+            self.tiling = tiling
 
     def set_threshold(self, mode: str = "off", ratio: float = 0.0, max_val: float = 1.0):
         """Dynamic thresholding of the samplers (include/ddif.h ddif_plan_set_threshold; sticky): "off" | "ddpm" (GaussianDiffusion clamp_type="dynamic":
@@ -869,6 +894,40 @@ def cond_assemble(lms_raw: torch.Tensor, pan_raw: torch.Tensor, division: float,
     lib.check(lib.dll.ddif_cond_assemble(_ptr(lms_raw), _ptr(pan_raw), float(division), B, Cc, P, H, W, int(wavelet_order), _ptr(out),
                                          _stream(lib, lms_raw.device)), "ddif_cond_assemble")
     return out
+
+
+def _tiles_op(name: str, src: torch.Tensor, out_shape, S, Cc, Hs, Ws, tile, overlap):
+    lib = get_lib()
+    _check_tensor(lib, src, name)
+    _check_current_device(src, name)
+    src = src.contiguous()
+    out = torch.empty(out_shape, dtype=torch.float32, device=src.device)
+    fn = getattr(lib.dll, name)
+    lib.check(fn(_ptr(src), int(S), int(Cc), int(Hs), int(Ws), int(tile), int(tile), int(overlap), _ptr(out), _stream(lib, src.device)), name)
+    return out
+
+
+def tiles_cut(scenes: torch.Tensor, tile: int, overlap: int, n_tiles: int) -> torch.Tensor:
+    """Scenes (S, C, Hs, Ws) -> tiles (S * n_tiles, C, tile, tile) on the overlapping grid (include/ddif.h ddif_tiles_cut); n_tiles = ny * nx of the grid."""
+    from .sharding import tile_grid
+
+    S, Cc, Hs, Ws = scenes.shape
+    ys, xs = tile_grid(Hs, Ws, tile, overlap)
+    if n_tiles != len(ys) * len(xs):
+        raise DdifError(f"tiles_cut: {n_tiles} tiles per scene, the grid has {len(ys)} x {len(xs)}")
+    return _tiles_op("ddif_tiles_cut", scenes, (S * n_tiles, Cc, tile, tile), S, Cc, Hs, Ws, tile, overlap)
+
+
+def tiles_blend(tiles: torch.Tensor, S: int, Hs: int, Ws: int, overlap: int) -> torch.Tensor:
+    """Tiles (S * ny * nx, C, tile, tile) -> scenes (S, C, Hs, Ws) by the weighted blend of include/ddif.h (ddif_tiles_blend)."""
+    n, Cc, th, tw = tiles.shape
+    if th != tw:
+        raise DdifError(f"tiles_blend: square tiles expected, got {th}x{tw}")
+    from .sharding import tile_grid
+
+    ys, xs = tile_grid(Hs, Ws, th, overlap)
+    _check_shape(tiles, "tiles", (S * len(ys) * len(xs), Cc, th, tw))
+    return _tiles_op("ddif_tiles_blend", tiles, (S, Cc, Hs, Ws), S, Cc, Hs, Ws, th, overlap)
 
 
 def dynamic_threshold(x0: torch.Tensor, ratio: float, max_val: float, symmetric: bool):

@@ -596,6 +596,7 @@ class DPM_Solver:
                 clamp = None
             else:
                 plan.set_threshold("off")
+            plan.set_tiling(None)  # the solver runs on independent tiles (a tiled DDPM / DDIM run may have left the cached plan tiled)
             plan.set_cond(cond)
             tabs = dict(n_evals=steps, order=order,
                         t_model=[float((ts[k] - 1.0 / ns.total_N) * 1000.0) for k in range(steps)],
@@ -638,6 +639,7 @@ class DPM_Solver:
                 clamp = None
             else:
                 plan.set_threshold("off")
+            plan.set_tiling(None)
             with torch.no_grad():
                 if guidance is None:
                     plan.set_cond(cond)

@@ -294,6 +294,50 @@ DDIF_API int ddif_plan_get_threshold(ddif_plan_t plan, int* mode, float* ratio, 
  *   s_out[b] = max(quantile(|x_b|, ratio), max_val);  out = clamp(x, symmetric ? -s_b : 0, s_b) / s_b.   1 <= n < 2^31; launches on the current device. */
 DDIF_API int ddif_dynamic_threshold(const float* x, int B, int64_t n, float ratio, float max_val, int symmetric, float* out, float* s_out, void* stream);
 
+/* ---- overlapping tiles with per-step fusion ------------------------------------------------------------ */
+
+/* The reference never tiles (diffusion_engine.py:373-377 feeds whole scenes); tiling is this build's way to scale, and these are its definitions --
+ * stated here and in ddif/sharding.py, and used by every kernel and test.
+ *   Grid, per axis: scene extent L, tile t, 0 <= overlap < t, L >= t.  stride = t - overlap;  n = 1 if L == t, else ceil((L - t) / stride) + 1;
+ *     origin p_k = min(k * stride, L - t): the last tile is shifted flush with the border, so any L >= t works and a pixel may lie in more than two
+ *     tiles per axis.  Tiles are numbered row-major (k = ky * nx + kx), scenes outermost (batch entry b = scene * ny * nx + k).
+ *   Weight of tile k at a scene pixel (y, x) it covers: w_k = wy * wx, wy = min(y - py_k + 1, py_k + t - y), wx alike: small integers, exact in fp32.
+ *   Blend of the values v_k of the covering tiles, in ascending k, fp32, no contraction:
+ *       den = sum w_k (exact);   r_k = w_k / den;   out = v_0 + sum_{k >= 1} r_k * (v_k - v_0)   added in that order, v_0 = the first covering tile.
+ *     A pixel with one cover is copied untouched, and equal inputs give exactly v_0: fusing what is already fused changes no bit. */
+#if defined(__HIP__) && !defined(DDIF_EMU)
+#define DDIF_INLINE static inline __attribute__((host)) __attribute__((device))
+#else
+#define DDIF_INLINE static inline
+#endif
+DDIF_INLINE int ddif_tile_count(int L, int t, int overlap) { return L == t ? 1 : (L - t + (t - overlap) - 1) / (t - overlap) + 1; }
+DDIF_INLINE int ddif_tile_origin(int k, int L, int t, int overlap) { return k * (t - overlap) < L - t ? k * (t - overlap) : L - t; }
+DDIF_INLINE int ddif_tile_weight(int y, int p, int t) { return y - p + 1 < p + t - y ? y - p + 1 : p + t - y; }
+
+/* The B batch entries of a plan are the tiles of n_scenes scenes of scene_h x scene_w on the grid above; the tile is the plan's own H x W. */
+typedef struct ddif_tiling {
+    int32_t n_scenes, scene_h, scene_w, overlap;
+} ddif_tiling;
+/* SURVEY.md 8f-2 (no reference line: a design decision of this build).  Sticky per plan, like ddif_plan_set_threshold; t == NULL turns it off (the
+ * default), and with it off every entry point behaves -- and launches -- exactly as before.  DDIF_ERR_INVALID unless B == n_scenes * ny * nx,
+ * 0 <= overlap < min(H, W) and scene_h >= H, scene_w >= W.  Under tiling:
+ *   - ddif_plan_sample_ddpm[_ex] / ddif_plan_sample_ddim[_ex] (all three objectives) take the unfused tail -- the update kernel as a launch of its own,
+ *     as under DDIF_THRESHOLD_DDPM -- and fuse x_{t-1} over the overlaps after EVERY step (one more launch, in place: every element of a scene that
+ *     lies in more than one tile is blended as above and written back to all its covers), so all covers of a pixel stay on one trajectory;
+ *   - the library's noise is keyed by SCENE pixel, for x_T (draw 0) and every step's z alike: Philox element
+ *         ((tile0 + scene) * C + c) * (scene_h * scene_w) + y * scene_w + x          (tile0 then counts scenes)
+ *     so every cover of a pixel draws the same normal and the stitched noise does not depend on the overlap.  Host-supplied x_T / noise stay per
+ *     tile, as without tiling: making them agree in the overlaps is the caller's business (cut them from a scene-sized field with ddif_tiles_cut);
+ *   - DDIF_THRESHOLD_DDPM in ddif_plan_sample_ddpm[_ex] is DDIF_ERR_INVALID (a per-tile s_b would differ between the covers of a pixel);
+ *   - ddif_plan_sample_dpmpp / _dpm / _dpm_guided are DDIF_ERR_INVALID: per-step fusion inside solver programs is not implemented -- sample the tiles
+ *     independently (tiling off) and blend once at the end with ddif_tiles_blend ("final" blending);
+ *   - ddif_plan_num_launches reports the tiled step: the step program + update + fusion (absent at overlap 0) + counter. */
+DDIF_API int ddif_plan_set_tiling(ddif_plan_t plan, const ddif_tiling* t);
+/* SURVEY.md 8f-2.  Scenes (S, C, Hs, Ws) -> tiles (S * ny * nx, C, tile_h, tile_w) on the grid above; NCHW device pointers; launches on the current device. */
+DDIF_API int ddif_tiles_cut(const float* scene, int S, int C, int Hs, int Ws, int tile_h, int tile_w, int overlap, float* tiles, void* stream);
+/* SURVEY.md 8f-2.  The inverse: tiles -> scenes by the blend above (the stitch of "final" blending; on the tiles of a fused run it reduces to copies). */
+DDIF_API int ddif_tiles_blend(const float* tiles, int S, int C, int Hs, int Ws, int tile_h, int tile_w, int overlap, float* scene, void* stream);
+
 /* Per-sample rows of p_losses beyond sqrt_ac / sqrt_1mac (B floats each, HOST or DEVICE like those):
  *   recon_xt, recon_out: x0 = recon_xt[b] * x_t - recon_out[b] * prediction (:708-713, :724, :735), the schedule pair of ddif_pred_tables gathered at t;
  *     required unless the plan predicts x_start;
